@@ -17,9 +17,12 @@ data-path collective; `value` = (N * K steps) / max-over-ranks time.  The same r
 DESIGN.md §8) and reports it as the extra object `frame_parallel` (strong scaling of one sample's latency); a watchdog
 bounds that leg so that a collective problem can never cost the headline line.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel = the MFMA implicit-GEMM family, timed per
-launch with events on the launch stream in a separate pass) and `cpu_baseline` (the oracle's fp32 UNet forward on the
-host cores, bounded sample, FLOP-scaled to the metric's unit).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline; everything
+else is measured only with --full: the extra objects `roofline` (dominant kernel = the MFMA implicit-GEMM family, timed per
+launch with events on the launch stream in a separate pass), `reference_shape`, `prompt_batch`, the N > 1 frame-parallel leg,
+the complete samples (24-view + VAE, CLIP towers, LGM-refined, I2VGen), `simulated_rank`, `other_dtype` and `cpu_baseline`
+(the oracle's fp32 UNet forward on the host cores, bounded sample, FLOP-scaled to the metric's unit); the --no-* options
+trim a --full run.  --dump-outputs DIR writes the latent the last timed step left (rank 0) as DIR/latent.npy (float32).
 """
 import argparse
 import ctypes
@@ -129,6 +132,24 @@ def cpu_baseline(frames, cores, shape, threads=None, budget=None):
     return best if best else (None, threads, None)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each tensor as d/<name>.npy in float32 (what the timed path left, so that two builds can be compared output for
+    output).  Past DUMP_CAP_BYTES in all, each tensor is replaced by a fixed seeded sample of its flattened elements (<name>_sample.npy)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > DUMP_CAP_BYTES:
+            keep = max(1, a.numel() * DUMP_CAP_BYTES // total)      # (this tensor's share of the cap, in 4-byte elements)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), a.numpy().astype(np.float32))
+
+
 def kernel_sources_sha16():
     """sha256 (first 16 hex digits) over the HIP sources the library is built from — what a committed counter measurement is tied to:
     `roofline.traffic` comes from profiles/*_gemm_traffic.json (PMC passes cannot run inside the timed process) and is marked stale
@@ -211,7 +232,7 @@ def run_fp_children(args, rank, world, local_launcher, port, dry_run=False):
                VMV_BENCH_LAUNCHER=f"frame-parallel child of {local_launcher}")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--latent", args.latent, "--frames", str(args.frames), "--fp-inprocess", "--frame-parallel-budget", str(args.frame_parallel_budget),
+           "--latent", args.latent, "--frames", str(args.frames), "--full", "--fp-inprocess", "--frame-parallel-budget", str(args.frame_parallel_budget),
            "--no-cpu-baseline", "--no-op-profile", "--no-sample", "--no-lgm", "--no-i2vgen", "--simulate-rank", "0"]
     if dry_run:
         cmd.append("--pg-dry-run")
@@ -259,6 +280,10 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--latent", type=str, default="40x64", help="latent HxW (40x64 = 320x512 px; 32x32 = reference 256 px)")
     ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline (roofline, reference shape, prompts "
+                    "per plan, N > 1 frame-parallel leg, samples, simulated rank, CPU baseline); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="after the timed steps, write the latent the last one left "
+                    "(rank 0) as DIR/latent.npy, float32 (a fixed seeded sample of it when it exceeds 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-op-profile", action="store_true")
     ap.add_argument("--dump-ops", type=str, default="", help="write the per-launch timing table to this file")
@@ -327,7 +352,7 @@ def main(argv=None):
         dist.all_reduce(pt)
         return int(pt[0])
 
-    fp_children = dist is not None and world > 1 and args.frames % world == 0 and not args.no_frame_parallel and not args.fp_inprocess
+    fp_children = args.full and dist is not None and world > 1 and args.frames % world == 0 and not args.no_frame_parallel and not args.fp_inprocess
     if args.pg_dry_run:
         fp_child = run_fp_children(args, rank, world, launcher, agreed_port(), dry_run=True) if fp_children else None
         if rank == 0:
@@ -386,6 +411,8 @@ def main(argv=None):
     from videomv_amd.dist import max_over_ranks
     dt = max_over_ranks(dt, cdev)                # the slowest rank defines the job time (no-op at N = 1)
     finite = bool(torch.isfinite(xt).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(latent=xt))
     steps_per_s = world * args.steps / dt
     ms_per_step = 1000.0 * dt / args.steps
     step_tflop = STEP_TFLOP.get((H, W))
@@ -432,7 +459,7 @@ def main(argv=None):
                         tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["flops"] else None) for k, v in fam.items()}, tot_ms
 
     roof = None
-    if rank == 0 and not args.no_op_profile:
+    if rank == 0 and args.full and not args.no_op_profile:
         eng = model.engine_for(2, args.frames, H, W, 77, dev, n_t=1, share_prefix=True)     # the plan the timed steps replayed
         rec = eng.S.recorded
         fam, _ = profile_plan(eng, dump=args.dump_ops)
@@ -467,7 +494,7 @@ def main(argv=None):
     #      default tile policy + rule and whatever the packaged table adds; `no_table_ms_per_step` is the same with VMV_TUNED=0 semantics
     #      (a fresh engine recorded while the table is hidden), i.e. what an UNTABLED shape gets
     ref_shape = None
-    if rank == 0 and world == 1 and (H, W) == (40, 64) and not args.no_op_profile:
+    if rank == 0 and world == 1 and (H, W) == (40, 64) and args.full and not args.no_op_profile:
         from videomv_amd import ops as _ops
 
         def time_shape(h, w, n=10):
@@ -510,7 +537,7 @@ def main(argv=None):
     #      sample's small levels do not fill 256 CUs, so b = 2 prompts in ONE plan of B = 4 row blocks (pair-major, fused CFG + DDIM update
     #      per sample: unet_t2v._forward_cfg_rows_batched) raise per-GPU throughput.  An extra object: `value` stays the 1-sample step.
     pbatch = None
-    if rank == 0 and world == 1 and not args.no_op_profile and not args.no_prompt_batch:
+    if rank == 0 and world == 1 and args.full and not args.no_op_profile and not args.no_prompt_batch:
         def time_batch(h, w, nb, n=8):
             x = torch.randn(nb, 4, args.frames, h, w, generator=g, device=dev)
             yb = torch.randn(nb, 77, 1024, generator=g, device=dev)
@@ -568,7 +595,7 @@ def main(argv=None):
         fence()
         fpar = run_fp_children(args, rank, world, launcher, agreed_port())
         fence()
-    elif dist is not None and args.frames % world == 0 and not args.no_frame_parallel:
+    elif args.full and dist is not None and args.frames % world == 0 and not args.no_frame_parallel:
         import threading
         done = threading.Event()
         state = {"stage": "init"}
@@ -707,7 +734,7 @@ def main(argv=None):
 
     # ---- one complete 24-view sample: 50 DDIM steps + VAE decode of 24 frames in chunks of decoder_bs = 4
     sample = None
-    if rank == 0 and world == 1 and not args.no_sample:
+    if rank == 0 and world == 1 and args.full and not args.no_sample:
         from videomv_amd.registry import AUTO_ENCODER
         import videomv_amd.autoencoder  # noqa: F401
         from videomv_amd.pipeline import sample_views, decode_views
@@ -751,7 +778,7 @@ def main(argv=None):
     # ---- the once-per-prompt conditioning upstream of the loop: open_clip ViT-H/14 text (2 prompts: caption + negative) and image
     #      towers on the same kernels (clip_embedder.py:187-201); full-size, random-init on the device
     clip = None
-    if rank == 0 and world == 1 and not args.no_sample:
+    if rank == 0 and world == 1 and args.full and not args.no_sample:
         try:
             from videomv_amd.clip_text import ClipTextEngine, ClipTextOptions, clip_text_shapes
             from videomv_amd.clip_vision import ClipVisionEngine, ClipVisionOptions, clip_vision_shapes
@@ -793,7 +820,7 @@ def main(argv=None):
     #      of which steps 20/30/40 send each CFG branch through VAE decode (4 views) -> LGM U-Net (415 M) -> 65 536
     #      Gaussians -> 24 renders at 512^2 -> VAE encode (24 views); full-size LGM, random weights
     lgm = None
-    if rank == 0 and world == 1 and not args.no_sample and not args.no_lgm:
+    if rank == 0 and world == 1 and args.full and not args.no_sample and not args.no_lgm:
         from videomv_amd.lgm import prepare_gs_data
         from videomv_amd.camera import entrance_camera_data
         with torch.device(dev):
@@ -913,7 +940,7 @@ def main(argv=None):
     #      zero-terminal-SNR schedule, guide 6 (i2vgen_xl_infer.yaml) — at the config's own 256-px shape (latent 32x32) and at the
     #      headline's 320x512 (latent 40x64)
     i2v = None
-    if rank == 0 and world == 1 and not args.no_sample and not args.no_i2vgen:
+    if rank == 0 and world == 1 and args.full and not args.no_sample and not args.no_i2vgen:
         try:
             import videomv_amd.unet_i2vgen  # noqa: F401
             with torch.device(dev):
@@ -980,7 +1007,7 @@ def main(argv=None):
     #      step = this rank's kernels + local copies (no wire time: the xGMI floor of its bytes is reported beside it); host ms per
     #      step = the time the Python thread needs to enqueue one step.  NOT a sample (peers' data = this rank's own).
     simr = None
-    if rank == 0 and world == 1 and args.simulate_rank > 1 and args.frames % args.simulate_rank == 0:
+    if rank == 0 and world == 1 and args.full and args.simulate_rank > 1 and args.frames % args.simulate_rank == 0:
         Wn = args.simulate_rank
         try:
             from videomv_amd.comm import SimComm
@@ -1081,7 +1108,7 @@ def main(argv=None):
             model.set_frame_parallel(None)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = os.cpu_count() or 1
         try:
             cores = len(os.sched_getaffinity(0))
@@ -1120,7 +1147,7 @@ def main(argv=None):
     # ---- the same timed region with the OTHER element type's kernels (child process: a process loads one library).  BASELINE
     #      configs[1] says bf16; the default is fp16 because only fp16 meets the stated parity tolerances
     alt = None
-    if rank == 0 and world == 1 and args.alt_dtype and not args.no_alt_dtype and not args.no_sample:
+    if rank == 0 and world == 1 and args.full and args.alt_dtype and not args.no_alt_dtype and not args.no_sample:
         import subprocess
         other = "bf16" if L.elem_name() == "fp16" else "fp16"
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--latent",

@@ -22,7 +22,7 @@ def _run(args, env_extra, timeout=300):
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_bench_gpus_n_spawns_n_ranks_and_counts_them(n):
-    r = _run(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--pg-dry-run"],
+    r = _run(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--full", "--pg-dry-run"],
              dict(VMV_BENCH_FAKE_DEVICES=str(n), VMV_BENCH_PG_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -46,7 +46,7 @@ def test_frame_parallel_children_rendezvous_under_torch_distributed_run():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pg-dry-run"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--pg-dry-run"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -58,7 +58,7 @@ def test_frame_parallel_children_rendezvous_under_torch_distributed_run():
 
 
 def test_no_frame_parallel_spawns_no_children():
-    r = _run(["--gpus", "2", "--pg-dry-run", "--no-frame-parallel"], dict(VMV_BENCH_FAKE_DEVICES="2", VMV_BENCH_PG_BACKEND="gloo"))
+    r = _run(["--gpus", "2", "--full", "--pg-dry-run", "--no-frame-parallel"], dict(VMV_BENCH_FAKE_DEVICES="2", VMV_BENCH_PG_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["fp_child"] is None and j["rccl_ranks"] == 2

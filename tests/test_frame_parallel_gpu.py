@@ -268,7 +268,7 @@ def test_bench_gpus_2_end_to_end_on_one_gpu(n):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--latent", "16x16", "--frames", "4",
-                        "--no-cpu-baseline", "--no-op-profile", "--frame-parallel-budget", "600"], cwd=root, env=env, capture_output=True, text=True, timeout=1500)
+                        "--full", "--no-cpu-baseline", "--no-op-profile", "--frame-parallel-budget", "600"], cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

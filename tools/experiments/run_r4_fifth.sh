@@ -6,7 +6,7 @@ cp videomv_amd/tuned_gemm.json gpurun_out/r4g_tuned_gemm.json
 tail -n 3 gpurun_out/r4g_autotune_lgm.log
 ( timeout 300 python tools/experiments/tuned_parity.py ) > gpurun_out/r4g_tuned_parity.log 2>&1
 grep -v amdgpu gpurun_out/r4g_tuned_parity.log | tail -8
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --simulate-rank 0 --no-i2vgen --no-op-profile"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --simulate-rank 0 --no-i2vgen --no-op-profile"
 ( VMV_TUNED=0 timeout 300 $B ) > gpurun_out/r4g_bench_t0.json 2> gpurun_out/r4g_bench_t0.err
 ( VMV_TUNED=1 timeout 300 $B ) > gpurun_out/r4g_bench_t1.json 2> gpurun_out/r4g_bench_t1.err
 for f in t0 t1; do python - <<PY

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-B="python bench.py --steps 10 --warmup 3 --no-sample --no-cpu-baseline --simulate-rank 0"
+B="python bench.py --full --steps 10 --warmup 3 --no-sample --no-cpu-baseline --simulate-rank 0"
 ( timeout 300 python tools/autotune_gemm.py --worlds 1 --latent 32x32 --merge --out videomv_amd/tuned_gemm.json ) > gpurun_out/r4f_autotune32.log 2>&1
 cp videomv_amd/tuned_gemm.json gpurun_out/r4f_tuned_gemm.json
 ( VMV_TUNED=0 timeout 200 $B --latent 32x32 ) > gpurun_out/r4f_b32_t0.json 2> gpurun_out/r4f_b32_t0.err

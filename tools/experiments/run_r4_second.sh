@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 ( timeout 600 python -m pytest tests/test_kernels_gpu.py -q -x -k "layernorm_folded or geglu" ) > gpurun_out/r4b_t_kern.log 2>&1
 ( timeout 900 python -m pytest tests/test_unet_gpu.py -q -x -k "blocks_match or full_size_architecture or i2vgen_properties or reference_golden" ) > gpurun_out/r4b_t_unet.log 2>&1
-B="python bench.py --steps 10 --warmup 3 --no-sample --no-cpu-baseline"
+B="python bench.py --full --steps 10 --warmup 3 --no-sample --no-cpu-baseline"
 ( VMV_TUNED=0 VMV_GEMM_XEPI=0 timeout 300 $B --simulate-rank 0 ) > gpurun_out/r4b_bench_xepi0.json 2> gpurun_out/r4b_bench_xepi0.err
 ( VMV_TUNED=0 VMV_GEMM_XEPI=1 timeout 300 $B --simulate-rank 0 --dump-ops gpurun_out/r4b_ops_xepi1.tsv ) > gpurun_out/r4b_bench_xepi1.json 2> gpurun_out/r4b_bench_xepi1.err
 ( timeout 900 python tools/autotune_gemm.py --worlds 1,8,4,2 --out videomv_amd/tuned_gemm.json ) > gpurun_out/r4b_autotune.log 2>&1

@@ -11,7 +11,7 @@ cp videomv_amd/tuned_gemm.json /tmp/new_table.json
 grep -c "tile 2[012]/ks[2-9]\|tile 2[012]/ks1" gpurun_out/r4m_autotune_a.log gpurun_out/r4m_autotune_b.log
 tail -n 1 gpurun_out/r4m_autotune_a.log gpurun_out/r4m_autotune_b.log
 cp /tmp/new_table.json gpurun_out/r4m_new_tuned_gemm.json
-B="python bench.py --steps 20 --warmup 5 --no-sample --no-cpu-baseline --no-op-profile"
+B="python bench.py --full --steps 20 --warmup 5 --no-sample --no-cpu-baseline --no-op-profile"
 run() { ( env "$@" timeout 200 $B $EXTRA ) 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); s=d.get('simulated_rank') or {}

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out
 cd $R; mkdir -p $O
 timeout 1500 python -m pytest tests/test_unet_gpu.py -x -q > $O/r6_pbatch2_tests.log 2>&1; tail -5 $O/r6_pbatch2_tests.log
-timeout 600 python bench.py --no-cpu-baseline --no-sample --simulate-rank 0 > $O/r6_pbatch2_bench.json 2> $O/r6_pbatch2_bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --no-sample --simulate-rank 0 > $O/r6_pbatch2_bench.json 2> $O/r6_pbatch2_bench.err
 python -c "
 import json
 d=json.loads([l for l in open('$O/r6_pbatch2_bench.json') if l.startswith('{')][-1])

@@ -2,7 +2,7 @@
 # round 6, 21st GPU call: b prompts per plan on the simulated 8-GPU rank (bench --simulate-rank 8)
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out
 cd $R; mkdir -p $O
-timeout 900 python bench.py --no-cpu-baseline --no-sample --no-op-profile --simulate-rank 8 > $O/r6_sim8_prompts.json 2> $O/r6_sim8_prompts.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-sample --no-op-profile --simulate-rank 8 > $O/r6_sim8_prompts.json 2> $O/r6_sim8_prompts.err
 python -c "
 import json
 d=json.loads([l for l in open('$O/r6_sim8_prompts.json') if l.startswith('{')][-1])

@@ -2,7 +2,7 @@
 # round 6, 24th GPU call: per-family table of the two-prompt plan beside the one-prompt plan at 24x32x32 (bench leg prompt_batch)
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out
 cd $R; mkdir -p $O
-timeout 600 python bench.py --no-cpu-baseline --no-sample --simulate-rank 0 > $O/r6_pbatch_families.json 2> $O/r6_pbatch_families.err
+timeout 600 python bench.py --full --no-cpu-baseline --no-sample --simulate-rank 0 > $O/r6_pbatch_families.json 2> $O/r6_pbatch_families.err
 python -c "
 import json
 d=json.loads([l for l in open('$O/r6_pbatch_families.json') if l.startswith('{')][-1])

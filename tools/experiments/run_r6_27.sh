@@ -6,7 +6,7 @@ cd $R; mkdir -p $O
 free -g | head -2; nproc
 for n in ${NS:-4 8}; do
   S=$(date +%s)
-  VMV_BENCH_PG_BACKEND=gloo VMV_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus $n --steps 2 --warmup 1 --latent ${LAT:-16x16} --frames 24 --no-cpu-baseline --no-op-profile --frame-parallel-budget 900 > $O/r6_share_gpu_n$n.json 2> $O/r6_share_gpu_n$n.err
+  VMV_BENCH_PG_BACKEND=gloo VMV_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --full --gpus $n --steps 2 --warmup 1 --latent ${LAT:-16x16} --frames 24 --no-cpu-baseline --no-op-profile --frame-parallel-budget 900 > $O/r6_share_gpu_n$n.json 2> $O/r6_share_gpu_n$n.err
   echo "n=$n rc=$? seconds=$(( $(date +%s) - S ))"
   python - <<PY
 import json

@@ -12,7 +12,7 @@ python tools/traffic_by_op.py table $O/r6_traffic_ops.json $O/tb_fetch $O/tb_wri
 cat $O/tb_table.log; head -30 $O/r6_gemm_traffic_by_kernel.tsv
 rm -rf $O/tb_fetch $O/tb_write
 cd /tmp
-python $R/bench.py --dump-ops $O/r6_ops_40x64_mid.tsv > $O/r6_bench_mid.json 2> $O/r6_bench_mid.err
+python $R/bench.py --full --dump-ops $O/r6_ops_40x64_mid.tsv > $O/r6_bench_mid.json 2> $O/r6_bench_mid.err
 python -c "
 import json; d=json.load(open('$O/r6_bench_mid.json'))
 print('ms_per_step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'whole', d['roofline']['whole_step']['frac'])

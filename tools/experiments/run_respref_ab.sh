@@ -2,7 +2,7 @@ set -u
 cd $GRAFT_REPO_ROOT
 O=gpurun_out
 timeout 900 python -m pytest tests/test_kernels_gpu.py -x -q -k "wide_tile or temporal_conv or conv3x3 or gemm_basic or xglds" > $O/c_xglds_tests.log 2>&1; echo "xglds tests rc=$?"; tail -3 $O/c_xglds_tests.log
-B="python bench.py --no-cpu-baseline --no-sample --no-lgm --no-i2vgen --simulate-rank 0 --steps 15 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --no-sample --no-lgm --no-i2vgen --simulate-rank 0 --steps 15 --warmup 3"
 for rep in 1 2; do
 for cfg in "VMV_LIB_DIR=$GRAFT_REPO_ROOT/ab_libs/before" "VMV_X=1"; do
   env $cfg timeout 300 $B --dump-ops $O/c_ops_$(echo $cfg | tr ' =/' '___' | tail -c 20).tsv 2> $O/c_step.err | python -c "
