@@ -39,8 +39,8 @@ int vmv_abi_version(void);
 #define VMV_ELEM_F16      0
 #define VMV_ELEM_BF16     1
 int vmv_elem_type(void);
-/* 1 if this build carries the experiment kernels (make EXPERIMENTS=1: VMV_TILE_S*, VMV_TILE_A*, the ablation hooks), else 0:
- * vmv_gemm then answers VMV_EINVAL to those forced tile ids */
+/* always 0: the experiment build that carried the retired tile ids (VMV_TILE_S*, VMV_TILE_A*, VMV_TILE_W256x256, VMV_TILE_Y256x128)
+ * is gone; vmv_gemm answers VMV_EINVAL to those forced tile ids.  Kept for ABI stability. */
 int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
@@ -164,11 +164,12 @@ typedef struct {
 #define VMV_TILE_PP256x160 12
 #define VMV_TILE_Q128x128 13   /* persistent, 4 waves, 2-stage ring, TWO blocks per CU (gemm_pglds.hip) */
 #define VMV_TILE_Q96x160  14
-#define VMV_TILE_S256x128 15   /* persistent, wave-specialised: 8 MFMA waves + 4 LDS-DMA loader waves (gemm_sglds.hip) */
-#define VMV_TILE_S192x160 16
-#define VMV_TILE_S256x160 17
-#define VMV_TILE_A128x160 18   /* A-stationary persistent kernel, deferred epilogue: K <= 320, wide N (gemm_astat.hip) */
-#define VMV_TILE_A128x128 19
+/* 15-19, 29, 31: RETIRED (measured and rejected kernels; vmv_gemm answers VMV_EINVAL) */
+#define VMV_TILE_S256x128 15   /* retired: persistent, wave-specialised: 8 MFMA waves + 4 LDS-DMA loader waves */
+#define VMV_TILE_S192x160 16   /* retired */
+#define VMV_TILE_S256x160 17   /* retired */
+#define VMV_TILE_A128x160 18   /* retired: A-stationary persistent kernel, deferred epilogue */
+#define VMV_TILE_A128x128 19   /* retired */
 #define VMV_TILE_X256x320 20   /* 8 waves x 64 x {160,128,64} wave tiles, four-stage ring of 32-deep chunks (gemm_xglds.hip): the
                                   long-K convolutions / temporal convolutions of the large levels; the 256 x 256 form also carries the folded
                                   LayerNorm (rowstat) and GEGLU epilogues; all three accept ksplit > 1 (plain epilogue, even splits of >= 4
@@ -189,16 +190,12 @@ typedef struct {
 #define VMV_TILE_TQA      28   /* q | k | v projection + temporal attention (gemm_tqa.hip, VMV_EPI_TATTN only): a wave keeps all F frames of 48 / F
                                   pixels x K = 320 in registers, W streams head-major through the LDS ring, the head's 24 x 24 attention is finished
                                   in registers; 48 % F == 0, N = 192 * heads <= 3840, optional folded LayerNorm (colsum + ln_eps) */
-#define VMV_TILE_W256x256 29   /* wide-wave register-staged kernel (gemm_wreg.hip): 4 waves x 128 x 128 of a 256 x 256 tile, accumulators in AGPRs,
-                                  global -> registers -> LDS; one plain linear segment, K % 32 == 0.  EXPERIMENT (make EXPERIMENTS=1; forced tile only): correct,
-                                  0.69 x of the 8-wave wide tile — DESIGN.md 10 */
+#define VMV_TILE_W256x256 29   /* retired: wide-wave register-staged kernel (4 waves x 128 x 128 of a 256 x 256 tile): 0.69 x of the 8-wave wide tile */
 
 #define VMV_TILE_X512x128 30   /* (ABI 11) gemm_xglds.hip with an 8 x 1 wave grid: 512 x 128 tile of 64 x 128 wave tiles — the N = 128 convolutions over
                                   millions of rows (the VAE's first level), where every 64 x 64-wave-tile kernel sits at 670 TFLOP/s; plain
                                   epilogue, no split-K */
-#define VMV_TILE_Y256x128 31   /* (ABI 11) gemm_xglds.hip in 256-thread blocks: 4 x 1 waves of 64 x 128, 256 x 128 tile, three-stage ring, TWO blocks per CU
-                                  (one's fill / epilogue under the other's main loop); plain, folded-LayerNorm and GEGLU epilogues; no split-K.  EXPERIMENT
-                                  (make EXPERIMENTS=1; forced tile only): correct, 0.62-0.92 x of the one-block forms — DESIGN.md 10 */
+#define VMV_TILE_Y256x128 31   /* retired: gemm_xglds.hip in 256-thread blocks, TWO blocks per CU: 0.62-0.92 x of the one-block forms */
 
 int vmv_gemm(const VmvGemmParams* p, void* stream);
 /* 1 if the host should record ONE VMV_EPI_TATTN launch for *p (a fused q | k | v + temporal-attention GEMM, epilogue already set)

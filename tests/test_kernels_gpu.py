@@ -78,7 +78,6 @@ def run_gemm(build, case, out_keys=("out",), cpu_ref=True):
                                         (300, 320, 64, L.TILE_P256x160), (257, 128, 192, L.TILE_P256x128),
                                         (513, 200, 72, L.TILE_P256x128), (2000, 1280, 1280, L.TILE_P256x160),
                                         (70000, 320, 320, L.TILE_P256x160), (70000, 384, 128, L.TILE_P256x128),
-                                        (640, 640, 640, L.TILE_W256x256), (2000, 1280, 1280, L.TILE_W256x256), (300, 320, 320, L.TILE_W256x256), (257, 128, 192, L.TILE_W256x256), (7000, 3840, 1280, L.TILE_W256x256), (513, 200, 160, L.TILE_W256x256),
                                         (66000, 160, 64, L.TILE_P256x160),
                                         (640, 640, 640, L.TILE_PP256x128), (1000, 960, 320, L.TILE_PP256x160),
                                         (300, 320, 64, L.TILE_PP256x160), (257, 128, 192, L.TILE_PP256x128),
@@ -88,22 +87,12 @@ def run_gemm(build, case, out_keys=("out",), cpu_ref=True):
                                         (513, 200, 72, L.TILE_Q128x128), (2000, 1280, 1280, L.TILE_Q96x160),
                                         (70000, 320, 320, L.TILE_Q96x160), (70000, 384, 128, L.TILE_Q128x128),
                                         (66000, 160, 64, L.TILE_Q96x160),
-                                        (640, 640, 640, L.TILE_S256x128), (1000, 960, 320, L.TILE_S192x160),
-                                        (300, 320, 64, L.TILE_S192x160), (257, 128, 192, L.TILE_S256x128),
-                                        (513, 200, 72, L.TILE_S256x128), (2000, 1280, 1280, L.TILE_S192x160),
-                                        (70000, 320, 320, L.TILE_S192x160), (70000, 384, 128, L.TILE_S256x128),
-                                        (66000, 160, 64, L.TILE_S192x160), (1000, 960, 320, L.TILE_S256x160),
-                                        (70000, 320, 320, L.TILE_S256x160), (2000, 1280, 1280, L.TILE_S256x160),
-                                        (66000, 100, 72, L.TILE_S256x160),
                                         # wide-tile kernel (gemm_xglds.hip): M / N tails, several tiles per block column, K = 128 .. 1280
                                         (640, 640, 640, L.TILE_X256x320), (1000, 960, 320, L.TILE_X256x320), (300, 320, 128, L.TILE_X256x320),
                                         (2000, 1280, 1280, L.TILE_X256x320), (70000, 320, 320, L.TILE_X256x320), (513, 200, 192, L.TILE_X256x320),
                                         (640, 640, 640, L.TILE_X256x256), (257, 256, 192, L.TILE_X256x256), (2000, 1280, 1280, L.TILE_X256x256),
                                         (66000, 512, 128, L.TILE_X256x256), (640, 640, 640, L.TILE_X256x128), (257, 128, 192, L.TILE_X256x128),
-                                        (70000, 384, 128, L.TILE_X256x128),
-                                        # round 6: 256-thread blocks, two per CU (gemm_xglds.hip WNV = 4)
-                                        (640, 640, 640, L.TILE_Y256x128), (257, 128, 192, L.TILE_Y256x128), (2000, 1280, 1280, L.TILE_Y256x128),
-                                        (70000, 384, 128, L.TILE_Y256x128)])
+                                        (70000, 384, 128, L.TILE_X256x128)])
 def test_gemm_linear_bias(M, N, K, tile):
     c = Case(a=rnd((M, K), 1), w=rnd((N, K), 2, K ** -0.5), b=torch.randn(N, generator=g(3)), out=torch.zeros(M, N, dtype=BF))
 
@@ -113,7 +102,7 @@ def test_gemm_linear_bias(M, N, K, tile):
     check(dev["out"], cpu["out"])
 
 
-@pytest.mark.parametrize("tile", [0, L.TILE_256x160, L.TILE_G128x160, L.TILE_P256x160, L.TILE_PP256x160, L.TILE_Q96x160, L.TILE_S192x160, L.TILE_S256x160])
+@pytest.mark.parametrize("tile", [0, L.TILE_256x160, L.TILE_G128x160, L.TILE_P256x160, L.TILE_PP256x160, L.TILE_Q96x160])
 def test_gemm_fp32_out_rowvec_act_residual(tile):
     M, N, K = 384, 320, 128
     c = Case(a=rnd((M, K), 1), w=rnd((N, K), 2, K ** -0.5), b=torch.randn(N, generator=g(3)),
@@ -127,7 +116,7 @@ def test_gemm_fp32_out_rowvec_act_residual(tile):
     check(dev["out"], cpu["out"], tol_l2=1e-3, tol_max=2e-3)
 
 
-@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128, L.TILE_S256x128, L.TILE_X256x256, L.TILE_W256x256, L.TILE_Y256x128])
+@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128, L.TILE_X256x256])
 def test_gemm_geglu(tile):
     M, I2, K = 200, 512, 128        # 2*I = 512 rows -> 256 outputs
     w = rnd((I2, K), 2, K ** -0.5)
@@ -145,8 +134,8 @@ def test_gemm_geglu(tile):
     check(dev["out"], x * torch.nn.functional.gelu(gate))
 
 
-@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128, L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160,
-                                  L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128, L.TILE_X512x128, L.TILE_Y256x128])
+@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128,
+                                  L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128, L.TILE_X512x128])
 @pytest.mark.parametrize("stride,ups,two_src,skip", [(1, 0, False, False), (2, 0, False, False), (1, 1, False, False),
                                                      (1, 0, True, True)])
 def test_gemm_conv3x3(stride, ups, two_src, skip, tile):
@@ -185,7 +174,7 @@ def test_gemm_conv3x3(stride, ups, two_src, skip, tile):
     check(dev["out"], ref.permute(0, 2, 3, 1).reshape(M, N))
 
 
-@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128, L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160])
+@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128])
 def test_gemm_temporal_conv_residual(tile):
     Bn, F_, Pp, Cc = 2, 5, 24, 64
     M = Bn * F_ * Pp
@@ -204,7 +193,7 @@ def test_gemm_temporal_conv_residual(tile):
     check(dev["out"], ref)
 
 
-@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128, L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160])
+@pytest.mark.parametrize("tile", [0, L.TILE_256x128, L.TILE_G128x128, L.TILE_P256x128, L.TILE_PP256x128, L.TILE_Q128x128])
 @pytest.mark.parametrize("ks", [2, 5])
 def test_gemm_splitk(ks, tile):
     M, N, K = 200, 256, 1280
@@ -285,7 +274,7 @@ def test_conv_halo_few_output_channels(n, H, W, Cin, N, fp32, ldo):
     assert float((old["out"].float()[:, :N] - dev["out"].float()[:, :N]).abs().max().cpu()) <= (2e-3 if fp32 else 2e-2) * float(ref.abs().max())
 
 
-@pytest.mark.parametrize("tile", [L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160, L.TILE_256x160, L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128,
+@pytest.mark.parametrize("tile", [L.TILE_256x160, L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128,
                                   L.TILE_X512x128])
 def test_gemm_conv3x3_many_tiles(tile):
     """>= 2 tiles per persistent block (M = 2*24*40*64/2 rows), residual + per-image row vector, two sources + 1x1 skip."""
@@ -311,7 +300,7 @@ def test_gemm_conv3x3_many_tiles(tile):
     check(dev["out"], ref.permute(0, 2, 3, 1).reshape(M, N))
 
 
-@pytest.mark.parametrize("tile", [L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160, L.TILE_X256x320, L.TILE_X256x256, L.TILE_X512x128])
+@pytest.mark.parametrize("tile", [L.TILE_X256x320, L.TILE_X256x256, L.TILE_X512x128])
 def test_gemm_temporal_conv_many_tiles(tile):
     Bn, F_, Pp, Cc = 2, 24, 1280, 320
     M = Bn * F_ * Pp
@@ -740,25 +729,13 @@ def test_layernorm_stats_out(rows, Cc):
                                                (70000, 320, 320, False, 0), (513, 1280, 320, True, 0),
                                                (70000, 1280, 320, True, L.TILE_P256x128), (257, 128, 192, False, L.TILE_128x128),
                                                (300, 512, 64, True, L.TILE_128x128), (2000, 3840, 1280, False, 0),
-                                               # the A-stationary deferred-epilogue kernel: M tail, several panels per
-                                               # block (M > 128 x 256 CUs), N tail (N = 1000: not a multiple of 160 / 128)
-                                               (70001, 960, 320, False, L.TILE_A128x160), (70001, 2560, 320, True, L.TILE_A128x128),
-                                               (1000, 1000, 320, False, L.TILE_A128x160), (300, 640, 256, True, L.TILE_A128x128),
-                                               (129, 320, 320, False, L.TILE_A128x128), (50000, 960, 320, False, 0),
-                                               (50000, 2560, 320, True, 0),
+                                               (50000, 960, 320, False, 0), (50000, 2560, 320, True, 0),
                                                # round 4: the wide tile's 256 x 256 form with the folded LayerNorm and / or GEGLU in its epilogue
                                                # (gemm_xglds.hip EPI): M / N tails, several tiles per block column, K = 128 .. 1280, the L2 shapes
                                                (7680, 3840, 1280, False, L.TILE_X256x256), (7680, 10240, 1280, True, L.TILE_X256x256),
                                                (300, 512, 128, False, L.TILE_X256x256), (513, 768, 192, True, L.TILE_X256x256),
                                                (1000, 1000, 320, False, L.TILE_X256x256), (2001, 1280, 640, True, L.TILE_X256x256),
-                                               (7680, 3840, 1280, False, 0), (7680, 10240, 1280, True, 0),
-                                               # round 6: the same epilogues in 256-thread blocks, two per CU (gemm_xglds.hip WNV = 4)
-                                               (7680, 3840, 1280, False, L.TILE_Y256x128), (7680, 10240, 1280, True, L.TILE_Y256x128),
-                                               (300, 512, 128, False, L.TILE_Y256x128), (513, 768, 192, True, L.TILE_Y256x128),
-                                               (1000, 1000, 320, False, L.TILE_Y256x128), (2001, 1280, 640, True, L.TILE_Y256x128),
-                                               # round 6: the wide-wave register-staged kernel (gemm_wreg.hip)
-                                               (7680, 3840, 1280, False, L.TILE_W256x256), (7680, 10240, 1280, True, L.TILE_W256x256), (513, 768, 192, True, L.TILE_W256x256),
-                                               (1000, 1000, 320, False, L.TILE_W256x256)])
+                                               (7680, 3840, 1280, False, 0), (7680, 10240, 1280, True, 0)])
 def test_gemm_layernorm_folded(M, N, K, geglu, tile):
     """y = Linear(LayerNorm(x)) as ONE GEMM on the raw rows (packing.fold_layernorm + rowstat / colsum epilogue) against
     the unfused definition, x with a large per-row offset (mean / sigma ~ 3) to exercise the cancellation."""
@@ -840,31 +817,6 @@ def test_gemm_layernorm_inline_eligibility():
     for p in bad:
         assert lib.vmv_gemm_ln_inline_ok(C.byref(p)) == 0
         assert lib.vmv_gemm(C.byref(p), None) == -1          # VMV_EINVAL
-
-
-@pytest.mark.parametrize("M,N,K,geglu,bias,tile", [(40000, 640, 320, False, True, L.TILE_A128x160), (513, 1280, 320, True, True, L.TILE_A128x128),
-                                                   (900, 960, 256, False, False, L.TILE_A128x160), (33000, 1280, 320, True, False, L.TILE_A128x128)])
-def test_gemm_astat_plain(M, N, K, geglu, bias, tile):
-    """gemm_astat.hip without the LayerNorm fold (bias on / off, GEGLU on / off) against the interpreter; two runs bitwise
-    identical (fixed accumulation order, no atomics)."""
-    c = Case(a=rnd((M, K), 1), w=rnd((N, K), 2, K ** -0.5), b=torch.randn(N, generator=g(3)),
-             out=torch.zeros(M, N // 2 if geglu else N, dtype=BF))
-
-    def build(t):
-        return ops.gemm_params(M, N, ops.linear_segs([(t["a"], K, K)]), t["w"], t["out"], t["out"].shape[1],
-                               bias=t["b"] if bias else None, epilogue=L.EPI_GEGLU if geglu else L.EPI_NONE, tile=tile)
-    cpu = c.on("cpu")
-    I.gemm(build(cpu))
-    dev = c.on("cuda")
-    S = ops.Stream(record=False)
-    S.gemm(build(dev), "t")
-    torch.cuda.synchronize()
-    check(dev["out"], cpu["out"])
-    dev2 = c.on("cuda")
-    S.gemm(build(dev2), "t")
-    torch.cuda.synchronize()
-    assert torch.equal(dev2["out"], dev["out"])
-
 
 
 # ------------------------------------------------------------------------------------------------- row-stationary GEMM

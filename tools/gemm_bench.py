@@ -7,7 +7,7 @@ import torch
 from videomv_amd import _lib as L, ops
 
 BF = L.elem()
-N160 = (L.TILE_128x160, L.TILE_256x160, L.TILE_G128x160, L.TILE_P256x160, L.TILE_PP256x160, L.TILE_Q96x160, L.TILE_S192x160, L.TILE_S256x160, L.TILE_A128x160)
+N160 = (L.TILE_128x160, L.TILE_256x160, L.TILE_G128x160, L.TILE_P256x160, L.TILE_PP256x160, L.TILE_Q96x160)
 
 
 def bench(fn, reps=20):
@@ -84,31 +84,14 @@ def main():
                 line += "      -    "; continue
             if tile in (L.TILE_RS, L.TILE_RS512, L.TILE_RS256) and (kind in ("conv", "tconv") or C not in (320, 640) or (tile == L.TILE_RS512 and C != 320)):
                 line += "      -    "; continue
-            stamps = torch.zeros(8 * 64, dtype=torch.int64, device=dev) if os.environ.get("VMV_GEMM_ABLATE") in ("4", "7", "8") else None
+            ws = None
             ks = int(os.environ.get("VMV_BENCH_KSPLIT", "0"))
             if ks > 1:
-                stamps = torch.zeros(ks * M * N, device=dev)
+                ws = torch.zeros(ks * M * N, device=dev)
                 kw["ksplit"] = ks
-            p = ops.gemm_params(M, N, segs, w, out, No, bias=b, geom=geom, tile=tile, workspace=stamps, **kw)
+            p = ops.gemm_params(M, N, segs, w, out, No, bias=b, geom=geom, tile=tile, workspace=ws, **kw)
             ms = bench(lambda: S.gemm(p))
             line += f" t{tile}:{2.0 * M * N * K / ms / 1e9:7.1f}"
-            if stamps is not None and tile in (L.TILE_P256x128, L.TILE_P256x160, L.TILE_Q128x128, L.TILE_Q96x160, L.TILE_PP256x128, L.TILE_PP256x160):
-                t = stamps.cpu().view(-1, 4)
-                t = t[t[:, 0] > 0]
-                if tile in (L.TILE_PP256x128, L.TILE_PP256x160):
-                    t = stamps.cpu().view(-1, 8)[:2]
-                    base = int(t[0, 0])
-                    line += "\n      PP stamps chunk 8 (grp0 / grp1: LOAD start, reads issued, DMA issued, waits done, barrier, MFMAs issued, wait, barrier):\n      " + \
-                            "\n      ".join(" ".join(f"{int(v) - base:6d}" for v in r) for r in t)
-                elif len(t):
-                    base = int(t[0, 0])
-                    rows = [" ".join(f"{int(v) - base:7d}" for v in r) for r in t[:6]]
-                    line += "\n      stamps(block0; tile start / loop done / epi start / epi end):\n      " + "\n      ".join(rows)
-            if stamps is not None and tile in (L.TILE_S256x128, L.TILE_S192x160, L.TILE_S256x160, L.TILE_A128x160):
-                t = stamps.cpu().view(-1, 8)[:int(os.environ.get("VMV_STAMP_ROWS", "40"))]
-                base = int(t[0, 0])
-                line += "\n   chunk: loader[before wait, after wait, after B, after issue]  mfma[before B, after B]\n   " + \
-                        "\n   ".join(f"{i:3d}: " + " ".join(f"{int(v) - base:7d}" for v in r[:6]) for i, r in enumerate(t))
         print(line, flush=True)
 
 

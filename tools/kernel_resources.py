@@ -1,14 +1,19 @@
 #!/usr/bin/env python
 """Register / spill / scratch summary of every kernel in the production library, from the compiler's resource-usage remarks that
-videomv_amd/csrc/compile_checked.sh keeps next to each object (build/<elem>/<src>.o.res).
-    python tools/kernel_resources.py [f16|bf16] > profiles/r3_kernel_resources.txt
+videomv_amd/csrc/compile_checked.sh keeps next to each object (<build>/<elem>/<src>.o.res).
+    python tools/kernel_resources.py [f16|bf16] [BUILD] > profiles/r3_kernel_resources.txt
+BUILD is the Makefile's object directory (default build; relative to videomv_amd/csrc).  Exits non-zero when it holds no reports.
 (The Makefile refuses a kernel with vgpr spills; this file is the record the judge asked for.)"""
 import glob, os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 elem = sys.argv[1] if len(sys.argv) > 1 else "f16"
+build = os.path.join(ROOT, "videomv_amd", "csrc", sys.argv[2] if len(sys.argv) > 2 else "build")
+reports = sorted(glob.glob(os.path.join(build, elem, "*.o.res")))
+if not reports:
+    sys.exit(f"error: no resource reports (*.o.res) under {os.path.join(build, elem)}: build the library first (make -C videomv_amd/csrc)")
 rows = []
-for f in sorted(glob.glob(os.path.join(ROOT, "videomv_amd", "csrc", "build", elem, "*.o.res"))):
+for f in reports:
     cur = None
     for l in open(f):
         m = re.search(r"remark: Function Name: (\S+)", l)
@@ -16,7 +21,7 @@ for f in sorted(glob.glob(os.path.join(ROOT, "videomv_amd", "csrc", "build", ele
             cur = dict(src=os.path.basename(f)[:-6], name=m.group(1)); rows.append(cur); continue
         if cur is None:
             continue
-        for key, pat in (("sgpr", r" SGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+        for key, pat in (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                          ("sspill", r"SGPRs Spill: (\d+)"), ("vspill", r"VGPRs Spill: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"),
                          ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
             m = re.search(pat, l)

@@ -47,7 +47,7 @@ ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 TILE_AUTO, TILE_128x128, TILE_128x160, TILE_128x64, TILE_64x64, TILE_256x128, TILE_256x160 = 0, 1, 2, 3, 4, 5, 6
 TILE_G128x128, TILE_G128x160, TILE_P256x128, TILE_P256x160, TILE_PP256x128, TILE_PP256x160 = 7, 8, 9, 10, 11, 12
 TILE_Q128x128, TILE_Q96x160 = 13, 14
-TILE_S256x128, TILE_S192x160, TILE_S256x160 = 15, 16, 17
+TILE_S256x128, TILE_S192x160, TILE_S256x160 = 15, 16, 17      # (15-19, 29, 31: retired ids, vmv.h — the library answers VMV_EINVAL)
 TILE_A128x160, TILE_A128x128 = 18, 19
 TILE_X256x320, TILE_X256x256, TILE_X256x128 = 20, 21, 22
 TILE_RS, TILE_RS512, TILE_RS256, TILE_HALO, TILE_TFR, TILE_TQA, TILE_W256x256, TILE_X512x128, TILE_Y256x128 = 23, 24, 25, 26, 27, 28, 29, 30, 31

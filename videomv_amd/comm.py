@@ -86,14 +86,14 @@ class FrameComm:
         # handle (VmvComm*): with RCCL underneath the collectives are recorded INTO the plans (VMV_OP_COMM) and issued by the C
         # replay loop on the replay's stream — one host call per forward instead of one Python collective per plan segment
         # (DESIGN.md §8).  Created on first use (collective: every rank of the group records its first plan at the same point);
-        # VMV_COMM_NATIVE=0 keeps the torch.distributed calls (the gloo path always does).
+        # the gloo path keeps the torch.distributed calls.
         self._handle, self._handle_tried = None, False
 
     @property
     def handle(self):
         if not self._handle_tried:
             self._handle_tried = True
-            if self.backend == "nccl" and not self.local_only and os.environ.get("VMV_COMM_NATIVE", "1") != "0" and torch.cuda.is_available():
+            if self.backend == "nccl" and not self.local_only and torch.cuda.is_available():
                 try:
                     self._handle = native_comm(self.group, torch.device("cuda", torch.cuda.current_device()))
                 except Exception as e:      # (the torch.distributed path needs nothing from libvmv: keep going on it)

@@ -18,7 +18,6 @@
 //            private 16-KB stage.
 #include "common.h"
 #include "gemm_glds_common.h"       // LDS-DMA helper, buffer descriptor constants
-#include <cstdlib>
 
 namespace {
 
@@ -28,13 +27,8 @@ VMV_DEV long seq_base(const VmvSeqMap& m, int o) {
 VMV_DEV int k_swz(int key) { return (((key >> 3) & 3) << 1) | ((key >> 1) & 1); }
 
 constexpr float NEG_BIG = -1.0e30f;
-#ifndef VMV_ATTN_STAGES
-#define VMV_ATTN_STAGES 2   // K / V ring depth of the 4-waves-per-problem kernels (head_dim 32 / 64).  3 (DMA of tile kt + 2 issued in tile kt's
-                            // softmax phase, a tile to land) measured SLOWER on one box: L0 self 592 -> 617-627 us, L1 80 -> 96, cross 47 -> 56
-#endif
-#ifndef VMV_ATTN_ABLATE
-#define VMV_ATTN_ABLATE 0   // experiments (tools/experiments/run_attn_ablate.sh): 1 no exp, 2 no softmax VALU, 3 no PV MFMAs, 4 no K/V restaging, 5 = 4 + no barrier
-#endif
+constexpr int ATTN_STAGES = 2;  // K / V ring depth of the 4-waves-per-problem kernels (head_dim 32 / 64).  3 (DMA of tile kt + 2 issued in tile kt's
+                                // softmax phase, a tile to land) measured SLOWER on one box: L0 self 592 -> 617-627 us, L1 80 -> 96, cross 47 -> 56
 
 // QT = 16-query tiles per wave (QT = 4: 64 queries per wave, 256 per block — every K / V fragment read from LDS and
 // every staged K / V tile then serves twice the MFMAs; the LDS port, shared by all the blocks of a CU, is what bounds the
@@ -48,9 +42,9 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
     static_assert(D == 64 || ((D == 32 || D == 128) && WPP == 4), "head_dim 64, or 32 / 128 on the 4-waves-per-problem variant");
     constexpr int KK = D / 32, DT = D / 16, SLOTS = D / 8, SLOG = (D == 128) ? 4 : (D == 64) ? 3 : 2;
     constexpr int KBYTES = (D == 128) ? 16384 : 8192, STAGE = 2 * KBYTES;       // staged K tile (then the V tile) / one stage
-    // WPP = 4 ring depth (VMV_ATTN_STAGES, default 2).  Three stages (48 KB): the DMA of tile kt + 2 goes out after tile kt's softmax
+    // WPP = 4 ring depth (ATTN_STAGES = 2).  Three stages (48 KB): the DMA of tile kt + 2 goes out after tile kt's softmax
     // and has a whole tile to land; with two stages it goes out at the top of the tile, among the S^T MFMAs — which measured faster.
-    constexpr int NST = (WPP == 4 && D != 128) ? VMV_ATTN_STAGES : 2;
+    constexpr int NST = (WPP == 4 && D != 128) ? ATTN_STAGES : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -61,10 +55,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
     int o, h, q0;
     bool wvalid = true;
     if constexpr (WPP == 4) {
-#ifndef VMV_ATTN_XCD_MAP
-#define VMV_ATTN_XCD_MAP 1
-#endif
-#if VMV_ATTN_XCD_MAP
         // XCD-aware block map: workgroups are handed out round-robin over the 8 XCDs in linear block order, so with the natural map
         // the query tiles that share one (problem, head)'s K / V land on eight different L2s and each re-fetches them from the fabric
         // (FETCH_SIZE: 1.2 GB per L0 self-attention launch for 236 MB of operands).  Bijection: the blocks of one XCD, in issue
@@ -75,9 +65,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
         const int logical = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
         const int pair = logical / nqt, qtile = logical - pair * nqt;
         o = pair / nh; h = pair - o * nh; q0 = (qtile * 4 + wave) * (16 * QT);
-#else
-        o = blockIdx.z; h = blockIdx.y; q0 = (blockIdx.x * 4 + wave) * (16 * QT);
-#endif
     } else {
         const int pidx = blockIdx.x * 4 + wave;
         wvalid = pidx < nproblems;
@@ -98,9 +85,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
         return reinterpret_cast<decltype(ptr)>(u);
     };
-#ifndef VMV_ATTN_VGPR_PTRS      // (A/B hook: -DVMV_ATTN_VGPR_PTRS keeps the round-2 form)
     qp = uniform_ptr(qp); kp = uniform_ptr(kp); vp = uniform_ptr(vp); op = uniform_ptr(op);
-#endif
     // row offsets inside one problem fit 32 bits (vmv_attention checks (N - 1) * s_row + head_dim < 2^30 elements): 64-bit
     // products of the row index kept their sign-extension registers alive across the main loop (three more spilled pairs)
     const int qs_row = (int)p.qm.s_row, ks_row = (int)p.km.s_row, vs_row = (int)p.vm.s_row, os_row = (int)p.om.s_row;
@@ -200,14 +185,9 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
         const u32x4_t* Ks;
         const uint16_t* Vt;
         if constexpr (WPP == 4) {
-#if VMV_ATTN_ABLATE == 4 || VMV_ATTN_ABLATE == 5
-            Ks = reinterpret_cast<const u32x4_t*>(region);
-            Vt = reinterpret_cast<const uint16_t*>(region + KBYTES);
-#else
             if constexpr (NST == 2) { if (kt + 1 < ntile) issue_tile(kt + 1, (kt + 1) & 1); }      // the other stage: last read one tile ago, behind a barrier
             Ks = reinterpret_cast<const u32x4_t*>(region + (kt % NST) * STAGE);
             Vt = reinterpret_cast<const uint16_t*>(region + (kt % NST) * STAGE + KBYTES);
-#endif
         } else {
             // One short problem per wave (the 24-frame temporal attention: HBM-bound).  Only V^T goes through LDS — the K
             // fragments are 16 contiguous bytes of a key row and are loaded straight into registers below — so a wave
@@ -287,10 +267,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
                 // (v_max3 through asm: fmaxf() is llvm.maxnum, which in IEEE mode first quiets every MFMA result with a
                 //  v_max x, x — 12 extra instructions per query tile; the cross-lane steps are gfx950's VALU lane swaps
                 //  instead of two ds_bpermute round trips)
-#if VMV_ATTN_ABLATE == 2
-                const float m_old = m_run[qt];
-                const float m_new = m_old;
-#else
                 float mx = vmax3(s[q2][0][0], s[q2][0][1], s[q2][0][2]);
                 mx = vmax3(mx, s[q2][0][3], s[q2][1][0]);
                 mx = vmax3(mx, s[q2][1][1], s[q2][1][2]);
@@ -302,7 +278,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
                 mx = xor16_max(mx);
                 const float m_old = m_run[qt];
                 const float m_new = xor32_max3(mx, m_old);
-#endif
                 const float nm = -m_new * sc;
                 const f32x2_t sc2 = {sc, sc}, nm2 = {nm, nm};
                 f32x2_t ps2 = {0.f, 0.f};
@@ -311,12 +286,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
                 for (int t = 0; t < 4; ++t) {           // packed fp32: one v_pk_fma / v_pk_add per two scores
                     f32x2_t a = {s[q2][t][0], s[q2][t][1]}, b = {s[q2][t][2], s[q2][t][3]};
                     a = a * sc2 + nm2; b = b * sc2 + nm2;
-#if VMV_ATTN_ABLATE == 1 || VMV_ATTN_ABLATE == 2
-                    const f32x2_t ea = a, eb = b;
-#else
                     const f32x2_t ea = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
                     const f32x2_t eb = {__builtin_amdgcn_exp2f(b.x), __builtin_amdgcn_exp2f(b.y)};
-#endif
                     pv[t][0] = ea.x; pv[t][1] = ea.y; pv[t][2] = eb.x; pv[t][3] = eb.y;
                     ps2 += ea; ps2 += eb;
                 }
@@ -364,11 +335,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
 #endif
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt) {
-#if VMV_ATTN_ABLATE == 3
-                        if (kk == 0 && dt == 0) { oacc[qt][0][0] += (float)vf[0] + (float)pf[qt][0][0] + (float)pf[qt][1][0]; }
-#else
                         oacc[qt][dt] = VMV_MFMA16(vf, pf[qt][kk], oacc[qt][dt], 0, 0, 0);
-#endif
                     }
                 }
             }
@@ -388,14 +355,9 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const VmvAttnParams p, con
             }
         }
         if constexpr (WPP == 4) {
-#if VMV_ATTN_ABLATE == 4
-            __syncthreads();
-#elif VMV_ATTN_ABLATE == 5
-#else
             // my pieces of tile kt + 1 have landed (three stages: those of tile kt + 2, issued above, may still be in flight) ...
             if (NST > 2 && kt + 2 < ntile) vmvg::wait_vmcnt<2 * NPIECE>(); else vmvg::wait_vmcnt<0>();
             __syncthreads();                                   // ... and everyone's; everyone is done reading tile kt
-#endif
         }
     }
 
@@ -579,7 +541,7 @@ extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
     if (p.causal && (hd != 64 || p.Nq != p.Nk)) return VMV_EINVAL;          // causal: self-attention on the general head_dim-64 kernel
     if (hd == 32) {                  // LGM MVAttention (core/attention.py:67-84): long sequences only
         if (p.n_outer > 65535 || p.heads > 65535) return VMV_ERANGE;
-        hipLaunchKernelGGL((attn_kernel<4, 2, 32>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), VMV_ATTN_STAGES * 16384, st, p, 0);
+        hipLaunchKernelGGL((attn_kernel<4, 2, 32>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
         return vmv_launch_status();
     }
     if (hd == 128) {                 // zero-padded wide heads (the CLIP image tower's head_dim 80 packed to 128: clip_vision.py)
@@ -590,9 +552,7 @@ extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
         return vmv_launch_status();
     }
     if (hd != 64) return VMV_EINVAL;
-    static int short_env = -1;
-    if (short_env < 0) { const char* e = getenv("VMV_ATTN_SHORT"); short_env = e ? atoi(e) : 1; }
-    if (p.Nq <= 32 && p.Nk <= 32 && short_env && !p.causal) {
+    if (p.Nq <= 32 && p.Nk <= 32 && !p.causal) {
         const int nproblems = p.n_outer * p.heads;
         hipLaunchKernelGGL(attn_short_kernel, dim3((nproblems + 3) / 4), dim3(256), 0, st, p, nproblems);
     } else if (p.Nq <= 32 && !p.causal) {
@@ -602,17 +562,15 @@ extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
         hipLaunchKernelGGL((attn_kernel<1, 2>), dim3((nproblems + 3) / 4), dim3(256), 32768, st, p, nproblems);
     } else {
         if (p.n_outer > 65535 || p.heads > 65535) return VMV_ERANGE;
-        static int qt_env = -1;
-        if (qt_env < 0) { const char* e = getenv("VMV_ATTN_QT"); qt_env = e ? atoi(e) : 0; }
         // (round 6: 64-query blocks — QT = 1, 84 registers, four blocks per CU — for the short problems (Nk <= 192 or Nq <= 192: cross-
         //  attention, third-level / middle self-attention) measured step-neutral: 47.88 / 47.91 vs 47.86 / 47.87 ms, attention family
         //  4.16 / 4.13 vs 4.17 / 4.17 ms, profiles/r6_attn_q64_step_ab.log — not kept)
         // 256-query blocks when that still leaves >= 2 blocks per CU and the key loop is long enough to matter
         const long blocks256 = (long)((p.Nq + 255) / 256) * p.heads * p.n_outer;
-        const bool big = qt_env == 4 || (qt_env == 0 && p.Nk >= 512 && blocks256 >= 512 && (p.Nq % 256 == 0 || p.Nq >= 2048));
-        if (p.causal) hipLaunchKernelGGL((attn_kernel<4, 2, 64, true>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), VMV_ATTN_STAGES * 16384, st, p, 0);
-        else if (big) hipLaunchKernelGGL((attn_kernel<4, 4>), dim3((p.Nq + 255) / 256, p.heads, p.n_outer), dim3(256), VMV_ATTN_STAGES * 16384, st, p, 0);
-        else hipLaunchKernelGGL((attn_kernel<4, 2>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), VMV_ATTN_STAGES * 16384, st, p, 0);
+        const bool big = p.Nk >= 512 && blocks256 >= 512 && (p.Nq % 256 == 0 || p.Nq >= 2048);
+        if (p.causal) hipLaunchKernelGGL((attn_kernel<4, 2, 64, true>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        else if (big) hipLaunchKernelGGL((attn_kernel<4, 4>), dim3((p.Nq + 255) / 256, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        else hipLaunchKernelGGL((attn_kernel<4, 2>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
     }
     return vmv_launch_status();
 }

@@ -8,8 +8,8 @@ out=$1; src=$2; hipcc=$3; shift 3
 awk '/remark:/{skip=2; next} skip>0 && (/^ +[0-9]+ \| / || /^ +\| +\^/){skip--; next} {skip=0; print}' "$out.res" | grep -v "^$" >&2
 [ $rc -ne 0 ] && exit $rc
 if grep -q "VGPRs Spill: [1-9]" "$out.res"; then
-    echo "error: $src: kernels with spilled VGPRs (fix them, or build the experiment sources with EXPERIMENTS=1 ALLOW_SPILLS=1):" >&2
+    echo "error: $src: kernels with spilled VGPRs:" >&2
     awk '/Function Name:/{name=$5} /VGPRs Spill: [1-9]/{print "    " name, $0}' "$out.res" | sed 's/\[-Rpass-analysis=kernel-resource-usage\]//; s/^\(.*\) .*remark: */\1  /' >&2
-    [ -z "$ALLOW_SPILLS" ] && { rm -f "$out"; exit 1; }
+    rm -f "$out"; exit 1
 fi
 exit 0

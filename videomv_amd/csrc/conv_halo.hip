@@ -22,12 +22,10 @@ using namespace vmvg;
 
 namespace {
 
-#ifndef VMV_CH_TH
-#define VMV_CH_TH 4            // tile height (image rows): 4 (one row per wave; 36-KB blocks, four per CU) or 8 (two rows; 55 KB, two per CU).
-                               // Measured at the VAE's head (24 x 320 x 512 x 128 -> 3): 369 us against 484 — the tile is bound by its DMA phase
-                               // (issue + latency), which more resident blocks hide, not by the 1.7 x instead of 1.4 x halo bytes
-#endif
-constexpr int CH_TH = VMV_CH_TH, CH_TW = 16, CH_HH = CH_TH + 2, CH_HW = CH_TW + 2, CH_HPX = CH_HH * CH_HW;      // 180 (108) halo pixels
+// CH_TH = tile height (image rows): 4 (one row per wave; 36-KB blocks, four per CU) or 8 (two rows; 55 KB, two per CU).
+// Measured at the VAE's head (24 x 320 x 512 x 128 -> 3): 369 us against 484 — the tile is bound by its DMA phase
+// (issue + latency), which more resident blocks hide, not by the 1.7 x instead of 1.4 x halo bytes
+constexpr int CH_TH = 4, CH_TW = 16, CH_HH = CH_TH + 2, CH_HW = CH_TW + 2, CH_HPX = CH_HH * CH_HW;      // 180 (108) halo pixels
 constexpr int CH_RPW = CH_TH / 4;                              // image rows per wave
 constexpr int CH_CMAX = 128;                                   // input channels per staged chunk
 constexpr int CH_HALO_BYTES = ((CH_HPX + 3) / 4) * 4 * CH_CMAX * 2;      // rounded up to whole 1-KB DMA instructions (4 pixels each)

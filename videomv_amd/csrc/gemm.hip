@@ -15,7 +15,6 @@
 //   * blockIdx -> tile is XCD-aware (8 XCDs, private L2): each XCD gets a contiguous range of tiles and walks
 //     the N tiles of one M tile first, so the activation tile is re-used out of that XCD's L2.
 #include "gemm_common.h"
-#include <cstdlib>
 
 using namespace vmvg;
 
@@ -24,18 +23,6 @@ int vmv_gemm_pglds_launch(const VmvGemmParams& p, int total_steps, int tile, hip
 bool vmv_gemm_pglds_supported(const VmvGemmParams& p);
 int vmv_gemm_xglds_launch(const VmvGemmParams& p, int total_steps, int tile, hipStream_t st);  // gemm_xglds.hip
 int vmv_gemm_xglds_epi_ok(const VmvGemmParams& p, int tile);                                      // gemm_xglds.hip
-#if defined(VMV_EXPERIMENTS)
-int vmv_gemm_sglds_launch(const VmvGemmParams& p, int total_steps, int tile, hipStream_t st);  // gemm_sglds.hip
-int vmv_gemm_astat_launch(const VmvGemmParams& p, int tile, hipStream_t st);                   // gemm_astat.hip
-int vmv_gemm_wreg_launch(const VmvGemmParams& p, hipStream_t st);                             // gemm_wreg.hip (round 6)
-bool vmv_gemm_wreg_supported(const VmvGemmParams& p);
-#else      // production build: the measured-and-rejected kernels are not in the library (make EXPERIMENTS=1)
-constexpr int VMV_NOT_BUILT = -101;
-static int vmv_gemm_sglds_launch(const VmvGemmParams&, int, int, hipStream_t) { return VMV_NOT_BUILT; }
-static int vmv_gemm_astat_launch(const VmvGemmParams&, int, hipStream_t) { return VMV_NOT_BUILT; }
-static int vmv_gemm_wreg_launch(const VmvGemmParams&, hipStream_t) { return VMV_NOT_BUILT; }
-static bool vmv_gemm_wreg_supported(const VmvGemmParams&) { return false; }
-#endif
 int vmv_gemm_rs_launch(const VmvGemmParams& p, int tile, hipStream_t st);                      // gemm_rs.hip
 bool vmv_gemm_rs_supported(const VmvGemmParams& p);
 int vmv_conv_halo_launch(const VmvGemmParams& p, hipStream_t st);                             // conv_halo.hip
@@ -47,12 +34,6 @@ bool vmv_gemm_tfr_preferred(const VmvGemmParams& p);
 int vmv_gemm_tqa_launch(const VmvGemmParams& p, hipStream_t st);                              // gemm_tqa.hip
 bool vmv_gemm_tqa_supported(const VmvGemmParams& p);
 bool vmv_gemm_tqa_preferred(const VmvGemmParams& p);
-#if defined(VMV_EXPERIMENTS)
-bool vmv_gemm_astat_eligible(const VmvGemmParams& p);
-#else
-static bool vmv_gemm_astat_eligible(const VmvGemmParams&) { return false; }
-#endif
-
 namespace {
 
 template <int WM, int WN>
@@ -282,83 +263,25 @@ int launch_cfg(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     return vmv_launch_status();
 }
 
-int gemm_policy() {
-    // VMV_GEMM_POLICY (A/B experiments): 0 = 128-row register-staged kernel only, 1 = + the 256-row LDS-DMA kernel,
-    // 2 (default) = + the persistent LDS-DMA kernel for short-K linears.
-    static int pol = -1;
-    if (pol < 0) {
-        const char* e = getenv("VMV_GEMM_POLICY");
-        pol = e ? atoi(e) : 2;
-    }
-    return pol;
-}
-
-int astat_policy() {
-    // VMV_GEMM_ASTAT (A/B experiments): 1 = the A-stationary deferred-epilogue kernel (gemm_astat.hip) takes the K <= 320,
-    // wide-N linears of the largest level (LayerNorm-folded qkv / q, GEGLU); 0 (default) = off.  Measured (round 2, same
-    // box): +12-25 % on the L0 qkv shapes in isolation, GEGLU +-2 %, but the full step gets 0.6 ms SLOWER — with every MFMA
-    // removed (VMV_GEMM_ABLATE=1) the kernel is no faster, without its stores +15-33 %: like the tile-per-item kernels it is
-    // bound by the CU's vector-memory path (DMA issue + in-order vmcnt behind store round trips), not by the matrix pipes.
-    static int pol = -1;
-    if (pol < 0) {
-        const char* e = getenv("VMV_GEMM_ASTAT");
-        pol = e ? atoi(e) : 0;
-    }
-    return pol;
-}
-
-// Step-level A/B hooks (experiments): VMV_GEMM_TILE_GEGLU / _LIN160 / _LIN128 force a tile id for the short-K (<= 24 chunks)
-// LINEAR GEMMs with GEGLU / N % 160 == 0 / other N, M >= 16384 (the L0 / L1 transformer linears); 0 = policy below.
-int tile_override(int which) {
-    static int ov[3] = {-1, -1, -1};
-    static const char* names[3] = {"VMV_GEMM_TILE_GEGLU", "VMV_GEMM_TILE_LIN160", "VMV_GEMM_TILE_LIN128"};
-    if (ov[which] < 0) { const char* e = getenv(names[which]); ov[which] = e ? atoi(e) : 0; }
-    return ov[which];
-}
-
-int x512_policy() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VMV_GEMM_X512"); v = e ? atoi(e) : 1; }
-    return v;
-}
-
-int xglds_policy() {
-    // VMV_GEMM_XGLDS (A/B experiments): 1 (default) = the wide-tile kernel (gemm_xglds.hip: 256 x 320 tiles, 64 x 160 wave tiles,
-    // four-stage ring of 32-deep chunks) takes the long-K GATHERED GEMMs — 3x3 convolutions, temporal convolutions — whose
-    // tiles fill the chip (the two large levels); 0 = off.  Measured (round 2, one box): L0 conv 806 -> 953, L0 temporal conv
-    // 683 -> 787, L1 conv 1040 -> 1140, L1 temporal conv 901 -> 980, VAE 512- / 256-channel convs +12 / +9 % (256 x 256 tiles) TFLOP/s;
-    // the plain-row linears (FF down, K = 1280 / 2560) are 1-5 % faster on the persistent kernel and the 128-channel VAE level on
-    // gemm_glds, and stay there; full step -0.9 ms.
-    static int pol = -1;
-    if (pol < 0) {
-        const char* e = getenv("VMV_GEMM_XGLDS");
-        pol = e ? atoi(e) : 1;
-    }
-    return pol;
-}
-
-int conv_halo_policy() {
-    // VMV_CONV_HALO (A/B experiments): 1 (default) = the halo-resident kernel takes the eligible few-channel 3 x 3 convolutions
-    static int pol = -1;
-    if (pol < 0) { const char* e = getenv("VMV_CONV_HALO"); pol = e ? atoi(e) : 1; }
-    return pol;
-}
-
 int pick_tile(const VmvGemmParams& p, int total_steps) {
     if (p.epilogue == VMV_EPI_TATTN) return VMV_TILE_TQA;      // fused q | k | v + temporal attention: one kernel (vmv_gemm checks eligibility)
     if (p.tile != VMV_TILE_AUTO) return p.tile;
     const int geglu = p.epilogue == VMV_EPI_GEGLU;
     // the short-K linears of the two large levels: rows resident in registers, W streamed, outputs per column pair (gemm_rs.hip)
-    if (gemm_policy() >= 2 && vmv_gemm_rs_preferred(p)) return VMV_TILE_RS;
+    if (vmv_gemm_rs_preferred(p)) return VMV_TILE_RS;
     // 3 x 3 convolutions with N <= 8 output channels (the VAE / UNet heads): halo tile + weights in LDS (conv_halo.hip)
-    if (gemm_policy() >= 2 && conv_halo_policy() && vmv_conv_halo_supported(p)) return VMV_TILE_HALO;
+    if (vmv_conv_halo_supported(p)) return VMV_TILE_HALO;
     // temporal convolutions whose frame-resident tiles fill the chip (gemm_tfr.hip); a GroupNorm folded into a temporal convolution
     // lives in that kernel only
-    if (gemm_policy() >= 2 && vmv_gemm_tfr_preferred(p)) return VMV_TILE_TFR;
+    if (vmv_gemm_tfr_preferred(p)) return VMV_TILE_TFR;
     if (p.gn_table && p.nseg == 3 && p.seg[0].mode == VMV_SEG_TEMPORAL) return VMV_TILE_TFR;
     if (p.gn_table) return VMV_TILE_RS;             // a folded GroupNorm lives in that kernel's prologue only (vmv_gemm checks eligibility)
-    if (gemm_policy() >= 2 && xglds_policy() && !geglu && p.ksplit <= 1 && !p.rowstat && !vmv_gemm_ln_inline(p) && total_steps >= 12 &&
-        (p.N % 320 == 0 || p.N % 256 == 0)) {
+    // The wide-tile kernel (gemm_xglds.hip: 256 x 320 tiles, 64 x 160 wave tiles, four-stage ring of 32-deep chunks) takes the long-K
+    // GATHERED GEMMs — 3x3 convolutions, temporal convolutions — whose tiles fill the chip (the two large levels).  Measured (round 2,
+    // one box): L0 conv 806 -> 953, L0 temporal conv 683 -> 787, L1 conv 1040 -> 1140, L1 temporal conv 901 -> 980, VAE 512- / 256-channel
+    // convs +12 / +9 % (256 x 256 tiles) TFLOP/s; the plain-row linears (FF down, K = 1280 / 2560) are 1-5 % faster on the persistent
+    // kernel and the 128-channel VAE level on gemm_glds, and stay there; full step -0.9 ms.
+    if (!geglu && p.ksplit <= 1 && !p.rowstat && !vmv_gemm_ln_inline(p) && total_steps >= 12 && (p.N % 320 == 0 || p.N % 256 == 0)) {
         bool any_gather = false;
         for (int i = 0; i < p.nseg; ++i) any_gather = any_gather || p.seg[i].mode != VMV_SEG_LINEAR;
         // one 256 x 320 (256 x 256) tile costs about 2 / 1.1 tiles of the 256 x 160 (256 x 128) kernel: take it when its rounds over
@@ -372,9 +295,9 @@ int pick_tile(const VmvGemmParams& p, int total_steps) {
     }
     // Round 6: N = 128 convolutions over >= 2 rounds of 512-row tiles (the VAE's first level: 1.6-3.9 M rows x 128 channels) — every
     // kernel with 64 x 64 wave tiles runs them at ~670 TFLOP/s (0.5 fragment reads per MFMA); the 8 x 1 wave grid's 64 x 128 wave tiles
-    // (gemm_xglds.hip WNV = 1) read 0.375.  VMV_GEMM_X512=0 keeps the old choice (A/B).
-    if (gemm_policy() >= 2 && xglds_policy() && x512_policy() && !geglu && p.ksplit <= 1 && !p.rowstat && !vmv_gemm_ln_inline(p) && p.N == 128 &&
-        total_steps >= 12 && p.wgroup_rows == 0 && !p.out_fp32 && (long)p.M >= 2L * 256 * 512) {
+    // (gemm_xglds.hip WNV = 1) read 0.375.
+    if (!geglu && p.ksplit <= 1 && !p.rowstat && !vmv_gemm_ln_inline(p) && p.N == 128 && total_steps >= 12 && p.wgroup_rows == 0 &&
+        !p.out_fp32 && (long)p.M >= 2L * 256 * 512) {
         bool any_gather = false;
         for (int i = 0; i < p.nseg; ++i) any_gather = any_gather || p.seg[i].mode != VMV_SEG_LINEAR;
         if (any_gather) return VMV_TILE_X512x128;
@@ -382,59 +305,32 @@ int pick_tile(const VmvGemmParams& p, int total_steps) {
     // Round 4: the transformer linears of the K = 1280 level that carry a folded LayerNorm (rowstat) and / or GEGLU — qkv, q, GEGLU of
     // the third level and the middle block — on the wide tile's 256 x 256 form (gemm_xglds.hip EPI): 780-870 -> ~1000 TFLOP/s.  Taken
     // when the tile grid makes at least ~1.7 rounds of the chip well filled (the same criterion as the persistent kernel's >= 2 tiles
-    // per CU, scaled to the twice-as-large tile); VMV_GEMM_XEPI=0 keeps the persistent kernel.
-    if (gemm_policy() >= 2 && xglds_policy() && (geglu || p.rowstat) && p.ksplit <= 1 && !vmv_gemm_ln_inline(p) && total_steps >= 20 &&
-        p.N % 256 == 0 && p.wgroup_rows == 0 && !p.out_fp32 && !p.rowvec && vmv_gemm_xglds_epi_ok(p, VMV_TILE_X256x256)) {
-        static int xepi = -1;
-        if (xepi < 0) { const char* e = getenv("VMV_GEMM_XEPI"); xepi = e ? atoi(e) : 1; }
+    // per CU, scaled to the twice-as-large tile).
+    if ((geglu || p.rowstat) && p.ksplit <= 1 && !vmv_gemm_ln_inline(p) && total_steps >= 20 && p.N % 256 == 0 && p.wgroup_rows == 0 &&
+        !p.out_fp32 && !p.rowvec && vmv_gemm_xglds_epi_ok(p, VMV_TILE_X256x256)) {
         bool lin = true;
         for (int i = 0; i < p.nseg; ++i) lin = lin && p.seg[i].mode == VMV_SEG_LINEAR;
         const long tiles = (long)((p.M + 255) / 256) * (p.N / 256);
         const long rounds = (tiles + 255) / 256;
-        if (xepi && lin && tiles >= 400 && (double)tiles / (double)(rounds * 256) >= 0.85) return VMV_TILE_X256x256;
+        if (lin && tiles >= 400 && (double)tiles / (double)(rounds * 256) >= 0.85) return VMV_TILE_X256x256;
     }
-    {
-        bool lin = p.ksplit <= 1 && total_steps <= 24 && p.M >= 16384;
-        for (int i = 0; i < p.nseg; ++i) lin = lin && p.seg[i].mode == VMV_SEG_LINEAR;
-        if (lin) {
-            const int o = tile_override(geglu ? 0 : (p.N % 160 == 0 ? 1 : 2));
-            if (o > 0) return o;
-        }
-    }
-#if defined(VMV_EXPERIMENTS)
-    if (gemm_policy() >= 2 && astat_policy() && p.N >= 640 && p.M >= 128 * 256 && vmv_gemm_astat_eligible(p))
-        return (!geglu && p.N % 160 == 0) ? VMV_TILE_A128x160 : VMV_TILE_A128x128;
-#endif
     auto padded = [&](int bn) { return ((p.N + bn - 1) / bn) * bn; };
     int best = VMV_TILE_128x128, best_pad = padded(128);
     if (!geglu && padded(160) <= best_pad) { best = VMV_TILE_128x160; best_pad = padded(160); }
     if (padded(64) < best_pad) { best = VMV_TILE_128x64; best_pad = padded(64); }
     if (p.M <= 64 && best == VMV_TILE_128x64) best = VMV_TILE_64x64;
-    if (gemm_policy() >= 1 && p.ksplit > 1 && p.M > 64 && (best == VMV_TILE_128x128 || best == VMV_TILE_128x160)) {
+    if (p.ksplit > 1 && p.M > 64 && (best == VMV_TILE_128x128 || best == VMV_TILE_128x160)) {
         // split-K (small-M levels): the 4-wave LDS-DMA kernel instead of the register-staged one (same 128-row tiles) ...
         const int bn = best == VMV_TILE_128x128 ? 128 : 160;
         best = best == VMV_TILE_128x128 ? VMV_TILE_G128x128 : VMV_TILE_G128x160;
         // ... unless the 8-wave 256-row tiles times the split make one round of the chip (one block per CU): twice the FLOPs per
         // LDS-DMA byte.  M = 1920, N = 1280 (the UNet's fourth level): 64 tiles x 4 splits = 256 blocks — conv 749 -> 805,
-        // conv 2560 -> 1280 893 -> 987, FF-down 559 -> 578 TFLOP/s (tools/experiments/run_l3_matrix.sh, same box)
+        // conv 2560 -> 1280 893 -> 987, FF-down 559 -> 578 TFLOP/s (same box)
         const long blocks256 = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn) * p.ksplit;
-        if (gemm_policy() >= 2 && p.M >= 1024 && blocks256 >= 192 && blocks256 <= 272)
+        if (p.M >= 1024 && blocks256 >= 192 && blocks256 <= 272)
             best = bn == 128 ? VMV_TILE_256x128 : VMV_TILE_256x160;
     }
-#if defined(VMV_EXPERIMENTS)
-    if (gemm_policy() >= 3 && p.ksplit <= 1 && !geglu && p.N % 160 == 0) {
-        // wave-specialised persistent kernel (gemm_sglds.hip): 8 MFMA waves + 4 loader waves per CU.  Measured against every
-        // other variant (tools/gemm_bench.py) it wins wherever its static round-robin over the 256 CUs is
-        // balanced: +15-25 % on the L0 convs / temporal convs, +3-10 % on the L0 / L1 linears; it loses when the tile count
-        // leaves the last round mostly empty (L2: 320 tiles = 1.25 rounds).
-        const long items = (long)((p.M + 191) / 192) * (p.N / 160);
-        const long rounds = (items + 255) / 256;
-        bool any_gather = false;
-        for (int i = 0; i < p.nseg; ++i) any_gather = any_gather || p.seg[i].mode != VMV_SEG_LINEAR;
-        if (items >= 256 && (double)items / (double)(rounds * 256) >= 0.8 && (gemm_policy() == 3 || any_gather)) return VMV_TILE_S192x160;
-    }
-#endif
-    if (gemm_policy() >= 1 && p.ksplit <= 1 && (best == VMV_TILE_128x128 || best == VMV_TILE_128x160)) {
+    if (p.ksplit <= 1 && (best == VMV_TILE_128x128 || best == VMV_TILE_128x160)) {
         // the 256-row kernel runs one block per CU: use it when its grid still fills the 256 CUs well
         const int bn = best == VMV_TILE_128x128 ? 128 : 160;
         const long tiles = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
@@ -448,7 +344,7 @@ int pick_tile(const VmvGemmParams& p, int total_steps) {
         for (int i = 0; i < p.nseg; ++i) linear = linear && p.seg[i].mode == VMV_SEG_LINEAR;
         const bool p160 = best == VMV_TILE_128x160;
         const long ptiles = (long)((p.M + (p160 ? 191 : 255)) / (p160 ? 192 : 256)) * ((p.N + bn - 1) / bn);
-        if (gemm_policy() >= 2 && linear && total_steps <= 24 && ptiles >= 2 * 256)
+        if (linear && total_steps <= 24 && ptiles >= 2 * 256)
             best = p160 ? VMV_TILE_P256x160 : VMV_TILE_P256x128;
         else if (big)
             best = best == VMV_TILE_128x128 ? VMV_TILE_256x128 : VMV_TILE_256x160;
@@ -458,17 +354,19 @@ int pick_tile(const VmvGemmParams& p, int total_steps) {
     return best;
 }
 
+// the retired tile ids (vmv.h): kernels measured and rejected, no longer in the library
+bool retired_tile(int t) {
+    return t == VMV_TILE_S256x128 || t == VMV_TILE_S192x160 || t == VMV_TILE_S256x160 || t == VMV_TILE_A128x160 || t == VMV_TILE_A128x128 ||
+           t == VMV_TILE_W256x256 || t == VMV_TILE_Y256x128;
+}
+
 // pick_tile + the constraints of the optional features (in-loop LayerNorm statistics, grouped weights, folded LayerNorm): the
 // configuration vmv_gemm launches first, or a negative VMV_E* code for a forced tile that cannot serve the request
 int final_tile(const VmvGemmParams& p, int total_steps) {
     int picked = pick_tile(p, total_steps);
-#if !defined(VMV_EXPERIMENTS)
-    if (picked == VMV_TILE_S256x128 || picked == VMV_TILE_S192x160 || picked == VMV_TILE_S256x160 || picked == VMV_TILE_A128x160 ||
-        picked == VMV_TILE_A128x128 || picked == VMV_TILE_W256x256 || picked == VMV_TILE_Y256x128) return VMV_EINVAL;
-#endif
+    if (retired_tile(picked)) return VMV_EINVAL;
     if (picked == VMV_TILE_HALO) return vmv_conv_halo_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TFR) return vmv_gemm_tfr_supported(p) ? picked : VMV_EINVAL;
-    if (picked == VMV_TILE_W256x256) return vmv_gemm_wreg_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TQA) return vmv_gemm_tqa_supported(p) && (p.tile == VMV_TILE_AUTO || p.tile == VMV_TILE_TQA) ? picked : VMV_EINVAL;
     const bool rs_tile = picked == VMV_TILE_RS || picked == VMV_TILE_RS512 || picked == VMV_TILE_RS256;
     if (rs_tile) return vmv_gemm_rs_supported(p) ? picked : VMV_EINVAL;      // (handles rowstat / colsum / grouped weights itself)
@@ -486,9 +384,9 @@ int final_tile(const VmvGemmParams& p, int total_steps) {
         else if (picked == VMV_TILE_256x160) picked = VMV_TILE_256x128;
         else if (!ok) picked = VMV_TILE_G128x128;
     }
-    if (p.rowstat && !((picked == VMV_TILE_X256x256 || picked == VMV_TILE_Y256x128) && vmv_gemm_xglds_epi_ok(p, picked)) && picked != VMV_TILE_A128x160 && picked != VMV_TILE_A128x128 && picked != VMV_TILE_P256x128 && picked != VMV_TILE_P256x160 && picked != VMV_TILE_Q128x128 &&
-        picked != VMV_TILE_Q96x160 && picked != VMV_TILE_128x128 && picked != VMV_TILE_128x160 && picked != VMV_TILE_128x64 &&
-        picked != VMV_TILE_64x64)
+    if (p.rowstat && !(picked == VMV_TILE_X256x256 && vmv_gemm_xglds_epi_ok(p, picked)) && picked != VMV_TILE_P256x128 && picked != VMV_TILE_P256x160 &&
+        picked != VMV_TILE_Q128x128 && picked != VMV_TILE_Q96x160 && picked != VMV_TILE_128x128 && picked != VMV_TILE_128x160 &&
+        picked != VMV_TILE_128x64 && picked != VMV_TILE_64x64)
         picked = (p.epilogue != VMV_EPI_GEGLU && p.N % 160 == 0) ? VMV_TILE_P256x160 : VMV_TILE_P256x128;
     return picked;
 }
@@ -506,29 +404,23 @@ bool ln_inline_ok(const VmvGemmParams& p) {
 
 }  // namespace
 
-extern "C" int vmv_has_experiments(void) {
-#if defined(VMV_EXPERIMENTS)
-    return 1;
-#else
-    return 0;
-#endif
-}
+extern "C" int vmv_has_experiments(void) { return 0; }      // (ABI: the experiment build is retired)
 
 extern "C" int vmv_gemm_ln_inline_ok(const VmvGemmParams* pp) { return pp && ln_inline_ok(*pp) ? 1 : 0; }
 
 extern "C" int vmv_gemm_rs_ok(const VmvGemmParams* pp) {
     if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
-    return gemm_policy() >= 2 && vmv_gemm_rs_preferred(*pp) ? 1 : 0;
+    return vmv_gemm_rs_preferred(*pp) ? 1 : 0;
 }
 
 extern "C" int vmv_gemm_tfr_ok(const VmvGemmParams* pp) {
     if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
-    return gemm_policy() >= 2 && vmv_gemm_tfr_preferred(*pp) ? 1 : 0;
+    return vmv_gemm_tfr_preferred(*pp) ? 1 : 0;
 }
 
 extern "C" int vmv_gemm_tqa_ok(const VmvGemmParams* pp) {
     if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
-    return gemm_policy() >= 2 && vmv_gemm_tqa_preferred(*pp) ? 1 : 0;
+    return vmv_gemm_tqa_preferred(*pp) ? 1 : 0;
 }
 
 extern "C" int vmv_gemm_pick_tile(const VmvGemmParams* pp) {
@@ -615,22 +507,10 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
             rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st);
             if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
             break;
-        case VMV_TILE_S256x128:
-            rc = vmv_gemm_sglds_launch(p, total_steps, VMV_TILE_S256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
-            break;
-        case VMV_TILE_S192x160:
-        case VMV_TILE_S256x160:
-            rc = vmv_gemm_sglds_launch(p, total_steps, picked, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
-            break;
         case VMV_TILE_X256x320:
         case VMV_TILE_X256x256:
         case VMV_TILE_X256x128:
         case VMV_TILE_X512x128:
-        case VMV_TILE_Y256x128:
             rc = vmv_gemm_xglds_launch(p, total_steps, picked, st);
             if (rc == VMV_GLDS_UNSUPPORTED && (p.rowstat || p.epilogue == VMV_EPI_GEGLU)) {      // the fused epilogues' other home
                 if (p.tile != VMV_TILE_AUTO) return VMV_EINVAL;
@@ -648,10 +528,6 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
             rc = vmv_gemm_tfr_launch(p, st);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
             break;
-        case VMV_TILE_W256x256:
-            rc = vmv_gemm_wreg_launch(p, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
-            break;
         case VMV_TILE_TQA:
             rc = vmv_gemm_tqa_launch(p, st);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
@@ -665,11 +541,6 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
         case VMV_TILE_RS256:
             rc = vmv_gemm_rs_launch(p, picked, st);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;      // (final_tile checked eligibility: a forced row tile that does not exist)
-            break;
-        case VMV_TILE_A128x160:
-        case VMV_TILE_A128x128:
-            rc = vmv_gemm_astat_launch(p, picked, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;      // (only reachable with a forced tile id)
             break;
         case VMV_TILE_Q128x128:
             rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_Q128x128, st);

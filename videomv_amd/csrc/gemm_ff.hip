@@ -18,7 +18,7 @@
 // W2 (320 rows x 64 B, gemm_xglds's 4-entry slot swizzle) by LDS-DMA into a two-stage ring; one barrier per chunk (60 MFMAs per
 // wave).
 //
-// Measured (M = 122 880, f16; tools/experiments/ff_bench.py and run_ff_ab.sh, one box): 383 us fused against 445 us for the two
+// Measured (M = 122 880, f16; tools/experiments/ff_bench.py, one box): 383 us fused against 445 us for the two
 // launches back to back in isolation, but inside a step the two launches take 214 + 165 us and the step is 51.61 ms with the
 // fused kernel against 51.52 ms without — so the engine leaves it OFF (VMV_FF_FUSED=1 opts in) and the entry point is kept for
 // callers whose memory, not time, is the constraint (no M x 4C hidden tensor).  Why it stops at 790 TFLOP/s: with one row tile
@@ -43,15 +43,8 @@ constexpr int FF_B1_BYTES = 8 * FF_C * 4, FF_B2_BYTES = FF_C * 4;
 constexpr int FF_LDS = 2 * FF_STAGE + FF_B1_BYTES + FF_B2_BYTES;
 static_assert(FF_LDS <= 160 * 1024, "LDS budget");
 
-#ifndef VMV_FF_PF1
-#define VMV_FF_PF1 1       // experiments: FF1 fragment prefetch distance in k-steps (4 fragments each)
-#endif
-#ifndef VMV_FF_PF2
-#define VMV_FF_PF2 3       // experiments: FF2 fragment prefetch distance in output tiles
-#endif
-#ifndef VMV_FF_ABLATE
-#define VMV_FF_ABLATE 0    // experiments (wrong results): 1 no MFMAs, 2 no fragment reads, 3 GELU -> identity, 4 no chunk barrier / DMA
-#endif
+constexpr int FF_PF1 = 1;       // FF1 fragment prefetch distance in k-steps (4 fragments each)
+constexpr int FF_PF2 = 3;       // FF2 fragment prefetch distance in output tiles
 
 VMV_DEV u32x4_t ff_swap16_xz_yw(u32x4_t v) {         // (gemm_rs.hip: padded v_permlane16_swap pair)
     uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
@@ -163,15 +156,11 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         const int slot = c & 1;
         // chunk c landed (mine: nothing but DMAs are in flight), then for every wave; every wave is also done with chunk c - 1,
         // whose slot takes chunk c + 1 — which then has the whole of chunk c's 60 MFMAs per wave to arrive
-#if VMV_FF_ABLATE == 4
-        if (c == 0) { wait_vmcnt<0>(); __builtin_amdgcn_s_barrier(); }
-#else
         wait_vmcnt<0>();
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (c + 1 < nchunk) issue_chunk(c + 1, slot ^ 1);
-#endif
         const unsigned char* w1b = smem + slot * FF_STAGE;
         const unsigned char* w2b = w1b + FF_W1_BYTES + f2off;
 
@@ -179,18 +168,12 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         f32x4_t h1[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) h1[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        constexpr int PF1 = VMV_FF_PF1, NB1 = PF1 + 1;
+        constexpr int PF1 = FF_PF1, NB1 = PF1 + 1;
         u32x4_t wf[NB1][4];
         auto rd1 = [&](const int kk, u32x4_t (&w)[4]) {
             const unsigned char* tp = w1b + foff[kk & 1] + 64 * kk;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#if VMV_FF_ABLATE == 2
-                w[t] = u32x4_t{(uint32_t)(uintptr_t)tp, 1u, 2u, (uint32_t)t};
-#else
-                w[t] = *reinterpret_cast<const u32x4_t*>(tp + t * (16 * 640));
-#endif
-            }
+            for (int t = 0; t < 4; ++t) w[t] = *reinterpret_cast<const u32x4_t*>(tp + t * (16 * 640));
         };
 #pragma unroll
         for (int kk = 0; kk < PF1; ++kk) rd1(kk, wf[kk % NB1]);
@@ -198,25 +181,15 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         for (int kk = 0; kk < FF_KS; ++kk) {
             if (kk + PF1 < FF_KS) rd1(kk + PF1, wf[(kk + PF1) % NB1]);
             __builtin_amdgcn_sched_barrier(0);
-#if VMV_FF_ABLATE == 1
-            h1[kk & 3].x += __uint_as_float(wf[kk % NB1][0].x ^ wf[kk % NB1][1].y ^ wf[kk % NB1][2].z ^ wf[kk % NB1][3].w ^ a[kk].x);
-#else
 #pragma unroll
             for (int t = 0; t < 4; ++t)
                 h1[t] = VMV_MFMA16(__builtin_bit_cast(elem8_t, wf[kk % NB1][t]), __builtin_bit_cast(elem8_t, a[kk]), h1[t], 0, 0, 0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- W2 fragments of the first output tiles go out under the GELU
-        constexpr int PF2 = VMV_FF_PF2, NB2 = PF2 + 1;
+        constexpr int PF2 = FF_PF2, NB2 = PF2 + 1;
         u32x4_t w2f[NB2];
-        auto rd2 = [&](const int j) -> u32x4_t {
-#if VMV_FF_ABLATE == 2
-            return u32x4_t{(uint32_t)(uintptr_t)w2b, 1u, 2u, (uint32_t)j};
-#else
-            return *reinterpret_cast<const u32x4_t*>(w2b + j * (16 * 64));
-#endif
-        };
+        auto rd2 = [&](const int j) -> u32x4_t { return *reinterpret_cast<const u32x4_t*>(w2b + j * (16 * 64)); };
 #pragma unroll
         for (int j = 0; j < PF2; ++j) w2f[j % NB2] = rd2(j);
         // ---- GEGLU of the two hidden tiles -> the B fragment of this chunk's k-step
@@ -227,12 +200,8 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
             const f32x4_t g0 = h1[1] + *reinterpret_cast<const f32x4_t*>(bb + 16);
             f32x4_t x1 = h1[2] + *reinterpret_cast<const f32x4_t*>(bb + 32);
             const f32x4_t g1 = h1[3] + *reinterpret_cast<const f32x4_t*>(bb + 48);
-#if VMV_FF_ABLATE == 3
-            x0 *= g0; x1 *= g1;
-#else
             x0.x *= gelu_erf_f(g0.x); x0.y *= gelu_erf_f(g0.y); x0.z *= gelu_erf_f(g0.z); x0.w *= gelu_erf_f(g0.w);
             x1.x *= gelu_erf_f(g1.x); x1.y *= gelu_erf_f(g1.y); x1.z *= gelu_erf_f(g1.z); x1.w *= gelu_erf_f(g1.w);
-#endif
             hf.x = pack_elem2(x0.x, x0.y); hf.y = pack_elem2(x0.z, x0.w);
             hf.z = pack_elem2(x1.x, x1.y); hf.w = pack_elem2(x1.z, x1.w);
         }
@@ -241,11 +210,7 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         for (int j = 0; j < FF_NT; ++j) {
             if (j + PF2 < FF_NT) w2f[(j + PF2) % NB2] = rd2(j + PF2);
             __builtin_amdgcn_sched_barrier(0);
-#if VMV_FF_ABLATE == 1
-            out[j].x += __uint_as_float(w2f[j % NB2].x ^ hf.x);
-#else
             out[j] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w2f[j % NB2]), __builtin_bit_cast(elem8_t, hf), out[j], 0, 0, 0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     }

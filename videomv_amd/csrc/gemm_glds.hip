@@ -14,18 +14,15 @@
 //   * 3-stage LDS ring (3 x 48/52 KB), loads run TWO chunks ahead of the MFMAs with counted s_waitcnt vmcnt(N)
 //     and one raw s_barrier per chunk:   wait(chunk t landed) -> barrier -> issue(chunk t+2) -> MFMA(chunk t).
 #include "gemm_glds_common.h"
-#include <cstdlib>
-#include <type_traits>
 
 using namespace vmvg;
 
 namespace {
 
-template <int WMW, int WN, int STAGES, int ablate, bool PP = false>
+template <int WMW, int WN, int STAGES, bool PP = false>
 __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(const VmvGemmParams p, const int tiles_m, const int tiles_n,
                                                               const int total_steps, const int steps_per_split, const int gm, const int tapmajor) {
     VMV_KERNEL_ENTER();
-    // ablate (experiments only, VMV_GEMM_ABLATE): 1 = skip the MFMAs + fragment reads, 2 = skip the LDS-DMA loads
     using Cfg = GlCfg<WMW, WN, STAGES>;
     constexpr int WM = 4;                         // 16-row MFMA tiles per wave along M (wave tile = 64 rows)
     constexpr int BN = Cfg::BN;
@@ -263,19 +260,10 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
             if (grp == 1) __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             int st = 0;
-            // ablate == 4: block 0 stamps s_memtime of its waves 0 and 4 at the phase edges of chunk 8 into p.workspace
-            unsigned long long* stamps = reinterpret_cast<unsigned long long*>(p.workspace);
-            auto stamp = [&](int t, int k) {
-                if constexpr (ablate == 4) {
-                    if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0 && t == 8 && stamps)
-                        stamps[grp * 8 + k] = __builtin_readcyclecounter();
-                }
-            };
             for (int t = 0; t < nsteps; ++t) {
                 // LOAD(t): the chunk's 2*(WM+WN) fragment reads INTERLEAVED with the LPT LDS-DMA pieces of chunk t+2, so that the
                 // LDS read port and the address/TA path work at the same time (issued back to back as two bursts they
                 // serialise: measured 430 + 560 cycles per wave against 740 cycles of MFMAs in the partner's phase).
-                stamp(t, 0);
                 int s2 = st + 2; if (s2 >= 3) s2 -= 3;
                 const bool more = issued < nsteps;
                 {
@@ -296,38 +284,29 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
                     int rd = 0;
 #pragma unroll
                     for (int k = 0; k < Cfg::LPT; ++k) {
-                        if (more && ablate != 2) {
+                        if (more) {
                             if (k < Cfg::NAI) VMV_BLDS16(c.a_rsrc, abase + k * (NW * 1024), a_off(c, k < Cfg::NAI ? k : 0), c.a_so);
                             else VMV_BLDS16(w_rsrc, wbase + wgrp[k - Cfg::NAI] * 1024, c.kvalid ? wvo[k - Cfg::NAI] : OOB, c.w_so);
                         }
                         const int upto = (NRD * (k + 1)) / Cfg::LPT;
-                        if constexpr (ablate != 1) {
 #pragma unroll
-                            for (int r = 0; r < NRD; ++r) if (r >= rd && r < upto) read_one(r);
-                        }
+                        for (int r = 0; r < NRD; ++r) if (r >= rd && r < upto) read_one(r);
                         rd = upto;
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    stamp(t, 1);
                     if (more) { advance(c.segk); ++issued; }
                 }
-                stamp(t, 2);
                 if (grp == 1) { if (more) wait_vmcnt<Cfg::LPT>(); else wait_vmcnt<0>(); }
                 __builtin_amdgcn_s_waitcnt(0xc07f);
-                stamp(t, 3);
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-                stamp(t, 4);
                 // MATRIX(t)
-                if constexpr (ablate != 1) { mma(a0, w0); mma(a1, w1); }
+                mma(a0, w0); mma(a1, w1);
                 __builtin_amdgcn_sched_barrier(0);
-                stamp(t, 5);
                 if (grp == 0) { if (more) wait_vmcnt<Cfg::LPT>(); else wait_vmcnt<0>(); }
-                stamp(t, 6);
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                stamp(t, 7);
                 st = st + 1 == 3 ? 0 : st + 1;
             }
             if (grp == 0) __builtin_amdgcn_s_barrier();
@@ -336,39 +315,28 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
         int issued = 0;
         const int pro = nsteps < GL_STAGES ? nsteps : GL_STAGES;
         for (int i = 0; i < pro; ++i) { issue(i); ++issued; }
-        if (ablate == 2 || ablate >= 5) issued = nsteps;       // 5: MFMAs only; 6: MFMAs + fragment reads (no barriers, no DMA)
         if (nsteps > 0) {
             if (pro == 3) wait_vmcnt<(GL_STAGES == 3 ? 2 : 0) * Cfg::LPT>(); else if (pro == 2) wait_vmcnt<Cfg::LPT>(); else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (ablate != 1 && ablate != 5) read_frags(0, 0, a0, w0);
-            else if (ablate == 5) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) { a0[i] = elem8_t{}; a1[i] = elem8_t{}; }
-#pragma unroll
-                for (int j = 0; j < WN; ++j) { w0[j] = elem8_t{}; w1[j] = elem8_t{}; }
-            }
+            read_frags(0, 0, a0, w0);
         }
         int st = 0;                                   // ring slot of chunk t
         for (int t = 0; t + 1 < nsteps; ++t) {        // (the last chunk is peeled below: no control-flow merge in here)
-            if constexpr (ablate != 1) {
-                if constexpr (ablate != 5) read_frags(st, 1, a1, w1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a0, w0);
-            }
+            read_frags(st, 1, a1, w1);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a0, w0);
             int stn = st + 1; if (stn == GL_STAGES) stn = 0;
             // chunk t+1 landed (mine): chunks up to t+STAGES-1 are in flight, so a 3-stage ring may leave one outstanding
             if (GL_STAGES == 3 && t + 2 < nsteps) wait_vmcnt<(GL_STAGES == 3 ? 1 : 0) * Cfg::LPT>(); else wait_vmcnt<0>();
             __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): my reads of slot st are done (builtin: the compiler's
                                                       // wait-count pass sees it and adds no second drain before the MFMAs)
-            if constexpr (ablate < 5) __builtin_amdgcn_s_barrier();             // ... for every wave: slot st is free, chunk t+1 is visible
+            __builtin_amdgcn_s_barrier();             // ... for every wave: slot st is free, chunk t+1 is visible
             asm volatile("" ::: "memory");
-            if constexpr (ablate != 1) {
-                if constexpr (ablate != 5) read_frags(stn, 0, a0, w0);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a1, w1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            read_frags(stn, 0, a0, w0);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a1, w1);
+            __builtin_amdgcn_sched_barrier(0);
             // address arithmetic, scalar loads of the segment table and the LDS-DMA issue run in the shadow of the
             // MFMA batch just issued (chunk t+3 -> the slot freed by the barrier above)
             if (issued < nsteps) { issue(st); ++issued; }
@@ -377,11 +345,9 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
             st = stn;
         }
         if (nsteps > 0) {
-            if constexpr (ablate != 1) {
-                if constexpr (ablate != 5) read_frags(st, 1, a1, w1);
-                mma(a0, w0);
-                mma(a1, w1);
-            }
+            read_frags(st, 1, a1, w1);
+            mma(a0, w0);
+            mma(a1, w1);
         }
     }
 
@@ -445,8 +411,7 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
                         if constexpr ((WN & 1) == 0) {
                             f32x4_t g = acc[(j + 1) % WN][i];
                             if (p.bias) g += *reinterpret_cast<const f32x4_t*>(p.bias + n + 16);
-                            if constexpr (ablate == 3) { v.x *= g.x; v.y *= g.y; v.z *= g.z; v.w *= g.w; }    // (experiment: no GELU)
-                            else { v.x *= gelu_erf_f(g.x); v.y *= gelu_erf_f(g.y); v.z *= gelu_erf_f(g.z); v.w *= gelu_erf_f(g.w); }
+                            v.x *= gelu_erf_f(g.x); v.y *= gelu_erf_f(g.y); v.z *= gelu_erf_f(g.z); v.w *= gelu_erf_f(g.w);
                         }
                         no = (n >> 5) * 16 + (n & 15);
                         tc = (tc >> 5) * 16 + (tc & 15);
@@ -498,25 +463,18 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
     }
 }
 
-// Run-wise K walk of the convolutions (kernel): on for M >= 16384 rows, off below; VMV_GLDS_TAPMAJOR = 0 / 1 forces it (A/B).
+// Run-wise K walk of the convolutions (kernel): on for M >= 16384 rows, off below.
 // Measured on one box: the walk cuts this kernel's convolution fetches 5.2 x -> 3.8 x of the algorithmic bytes at the UNet's third /
 // fourth level (what is left is W, streamed once into each of the 8 L2s: 240 tiles = one round), but those convolutions (M = 7680 /
 // 1920) run 1-4 % slower (L3 tconv 314 -> 303 TFLOP/s, conv L2 1018 -> 1008) and the step +0.25 ms (48.05 / 48.20 vs 47.87 / 47.89;
 // profiles/r6_tap2_*.log, r6b_gemm_traffic_by_kernel.tsv): there the fetches it saves come out of the Infinity Cache and were not
 // the bound.  Where A is the whole traffic — the VAE's 128-channel convolutions over 1.6-3.1 M rows (W = 295 KB) — it pays: encoder
 // first level 570 -> 672 / 503 -> 585 TFLOP/s, 48-view encode 22.4 -> 20.6 ms, decode 7.7 -> 7.4 (profiles/r6_lgm_step_bench*.log).
-int glds_tapmajor(const VmvGemmParams& p) {
-    static int v = -2;
-    if (v == -2) { const char* e = getenv("VMV_GLDS_TAPMAJOR"); v = e ? atoi(e) : -1; }
-    return v >= 0 ? v : (p.M >= 16384 ? 1 : 0);
-}
+int glds_tapmajor(const VmvGemmParams& p) { return p.M >= 16384 ? 1 : 0; }
 
 // rows of the tile group that shares W slices in an XCD's L2 (gemm_xglds.hip xglds_group_m; `conc` = blocks an XCD runs at once:
-// 32 CUs x 1 or 2 blocks).  VMV_GLDS_GM forces it (A/B; 1 = the round-5 order).
+// 32 CUs x 1 or 2 blocks).
 int glds_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc) {
-    static int env = -2;
-    if (env == -2) { const char* e = getenv("VMV_GLDS_GM"); env = e ? atoi(e) : -1; }
-    if (env >= 1) return env;
     if (tiles_n < 2 || tiles_m < 2) return 1;
     int best = 1, best_cost = BM + conc * BN;
     for (int gm = 2; gm <= conc; gm *= 2) {
@@ -537,33 +495,12 @@ int launch_glds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     const int tiles_n = (p.N + Cfg::BN - 1) / Cfg::BN;
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     const int sps = (total_steps + ks - 1) / ks;
-    static int ablate = -1;
-    if (ablate < 0) { const char* e = getenv("VMV_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
     dim3 grid(tiles_m * tiles_n, ks, 1);
     const int gm = glds_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, WMW == 2 ? 64 : 32);
-    auto go = [&](auto tag) -> int {
-        constexpr int AB = decltype(tag)::value;
-        static std::atomic<unsigned long long> attr_set{0};
-        if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_glds_kernel<WMW, WN, STAGES, AB, PP>), Cfg::LDS_BYTES)) return rc_attr;
-        VMV_LAUNCH((gemm_glds_kernel<WMW, WN, STAGES, AB, PP>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n,
-                           total_steps, sps, gm, glds_tapmajor(p));
-        return VMV_OK;
-    };
-    int rc;
-#if defined(VMV_EXPERIMENTS)       // (the ablation instantiations are not in the production library)
-    switch (ablate) {
-        case 1: rc = go(std::integral_constant<int, 1>{}); break;
-        case 2: rc = go(std::integral_constant<int, 2>{}); break;
-        case 3: rc = go(std::integral_constant<int, 3>{}); break;
-        case 4: rc = go(std::integral_constant<int, 4>{}); break;
-        case 5: rc = go(std::integral_constant<int, 5>{}); break;
-        case 6: rc = go(std::integral_constant<int, 6>{}); break;
-        default: rc = go(std::integral_constant<int, 0>{}); break;
-    }
-#else
-    rc = go(std::integral_constant<int, 0>{});
-#endif
-    if (rc != VMV_OK) return rc;
+    static std::atomic<unsigned long long> attr_set{0};
+    if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_glds_kernel<WMW, WN, STAGES, PP>), Cfg::LDS_BYTES)) return rc_attr;
+    VMV_LAUNCH((gemm_glds_kernel<WMW, WN, STAGES, PP>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, total_steps, sps, gm,
+               glds_tapmajor(p));
     return vmv_launch_status();
 }
 

@@ -17,7 +17,6 @@
 // Tile order: item v -> logical tile through the XCD-aware bijection, so the 32 CUs of an XCD work on 32 consecutive
 // tiles (same rows of A, neighbouring weight columns) in every round.
 #include "gemm_glds_common.h"
-#include <cstdlib>
 #include <type_traits>
 
 using namespace vmvg;
@@ -50,9 +49,9 @@ struct PgCfg {
 // LNS: the (mean, rstd) of a LayerNorm folded into this GEMM (vmv.h, VmvGemmParams.ln_eps) are accumulated from the A
 // fragments the MFMAs consume — the K loop of such a GEMM walks each row completely, a wave's lanes hold output row
 // m = frow for both the fragments and the accumulators — instead of being read from a statistics pass.
-template <int NWM, int WM, int WN, int ablate, bool IL, bool LNS = false>
+template <int NWM, int WM, int WN, bool LNS = false>
 __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel(const VmvGemmParams p, const int tiles_n, const int total_steps,
-                                                         const int nitems, const int panel_order) {
+                                                         const int nitems) {
     VMV_KERNEL_ENTER();
     using Cfg = PgCfg<NWM, WM, WN>;
     constexpr int BN = Cfg::BN;
@@ -71,17 +70,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
     auto item_tile = [&](int v, int& m0, int& n0) {      // XCD-aware bijection item -> tile (see gemm_glds.hip)
         const int q = nitems >> 3, r = nitems & 7;
         const int xcd = v & 7;
-        int idx = v >> 3;
-        if (panel_order) {
-            // Panels of 8 tile rows (8 * tiles_n consecutive tiles of this XCD's range): CU j of the XCD (idx = 32 round + j)
-            // keeps row j % 8 for the whole panel and walks its columns 4 at a time with the three CUs that share the row, so
-            // an A tile is fetched from HBM once per panel and re-read from L2 by the following rounds — in plain order every
-            // round of an XCD starts on fresh rows and each chunk of every tile waits for an HBM miss.
-            const int qx = q + (xcd < r ? 1 : 0);
-            const int P = 8 * tiles_n;
-            const int pb = (idx / P) * P, l = idx - pb;
-            if (pb + P <= qx) idx = pb + (l & 7) * tiles_n + (l >> 3);
-        }
+        const int idx = v >> 3;
         const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
         const int tn = logical % tiles_n;
         m0 = (logical / tiles_n) * BM;
@@ -130,11 +119,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         L_left = total_steps;
         enter_segment();
     };
-    // One chunk = LPT wave-instructions ("pieces": NAI of A, then NWI of W).  issue_one() sends them in a burst; the
-    // interleaved main loop (IL) sends them one at a time between MFMAs, half a chunk per MFMA phase: the texture path
-    // accepts one 1-KB wave-instruction every ~26 cycles per CU (tools/experiments/lds_dma_rate.hip: 91 GB/s per CU with 8
-    // waves), so a burst of 8 x LPT instructions after a barrier parks every wave in its issue slot for ~500 cycles with
-    // the MFMA pipes idle.
+    // One chunk = LPT wave-instructions ("pieces": NAI of A, then NWI of W); issue_one() sends them in a burst.
     struct ChunkCtx {
         __amdgpu_buffer_rsrc_t a_rsrc;
         unsigned char* abase;
@@ -154,11 +139,9 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         return c;
     };
     auto issue_piece = [&](const ChunkCtx& c, const int q) {      // q: compile-time after unrolling
-        if constexpr (ablate != 2) {
-            if (q < Cfg::NAI) VMV_BLDS16(c.a_rsrc, c.abase + q * (NW * 1024), c.kall ? avo[q < Cfg::NAI ? q : 0] : OOB, c.a_so);
-            else VMV_BLDS16(w_rsrc, c.wbase + wgrp[q >= Cfg::NAI ? q - Cfg::NAI : 0] * 1024,
-                            c.kall ? wvo[q >= Cfg::NAI ? q - Cfg::NAI : 0] : OOB, c.w_so);
-        }
+        if (q < Cfg::NAI) VMV_BLDS16(c.a_rsrc, c.abase + q * (NW * 1024), c.kall ? avo[q < Cfg::NAI ? q : 0] : OOB, c.a_so);
+        else VMV_BLDS16(w_rsrc, c.wbase + wgrp[q >= Cfg::NAI ? q - Cfg::NAI : 0] * 1024,
+                        c.kall ? wvo[q >= Cfg::NAI ? q - Cfg::NAI : 0] : OOB, c.w_so);
     };
     auto advance_chunk = [&]() {
         const VmvGemmSeg& sg = p.seg[s];
@@ -236,37 +219,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
 #pragma unroll
                 for (int i = 0; i < WM; ++i)
                     acc[j][i] = VMV_MFMA16(wf[j], af[i], acc[j][i], 0, 0, 0);
-        }
-    };
-
-    // One MFMA phase of the interleaved loop: the WM*WN MFMAs on (af, wf), with the WM+WN fragment reads of the NEXT phase
-    // (slot_n, kk_n -> afn, wfn) and pieces [Q0, Q1) of the chunk being loaded spread evenly between them.
-    constexpr int NM = WM * WN, NRD = WM + WN;
-    auto phase = [&](const elem8_t (&af)[WM], const elem8_t (&wf)[WN], elem8_t (&afn)[WM], elem8_t (&wfn)[WN],
-                     const int slot_n, const int kk_n, const bool dma, const ChunkCtx& cx, auto q0_tag, auto q1_tag) {
-        constexpr int Q0 = decltype(q0_tag)::value, Q1 = decltype(q1_tag)::value, ND = Q1 - Q0;
-        const u32x4_t* a = reinterpret_cast<const u32x4_t*>(smem + slot_n * Cfg::STAGE_BYTES) + (wave_m * 16 * WM + frow) * 8;
-        const u32x4_t* w = reinterpret_cast<const u32x4_t*>(smem + slot_n * Cfg::STAGE_BYTES + Cfg::A_BYTES) +
-                           (wave_n * 16 * WN + frow) * 8;
-        const int slot = (kk_n * 4 + fgrp) ^ fswz;
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const int j = m / WM, i = m % WM;
-            if constexpr (ablate != 1) acc[j][i] = VMV_MFMA16(wf[j], af[i], acc[j][i], 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < NRD; ++r)
-                if (((2 * r + 1) * NM) / (2 * NRD) == m) {
-                    if constexpr (ablate != 1) {
-                        if (r < WM) afn[r < WM ? r : 0] = __builtin_bit_cast(elem8_t, a[(r < WM ? r : 0) * 16 * 8 + slot]);
-                        else wfn[r >= WM ? r - WM : 0] = __builtin_bit_cast(elem8_t, w[(r >= WM ? r - WM : 0) * 16 * 8 + slot]);
-                    }
-                }
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-                if (((2 * d + 1) * NM) / (2 * ND) == m) {
-                    if (dma) issue_piece(cx, Q0 + d);
-                }
-            __builtin_amdgcn_sched_barrier(0);
         }
     };
 
@@ -429,8 +381,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
                     if constexpr ((WN & 1) == 0) {
                         const f32x4_t g = acc[(j + 1) % WN][i] +
                                           *reinterpret_cast<const f32x4_t*>(bias_lds + 16 * ((j + 1) % WN) + 4 * fgrp);
-                        if constexpr (ablate == 3) { v.x *= g.x; v.y *= g.y; v.z *= g.z; v.w *= g.w; }
-                        else { v.x *= gelu_erf_f(g.x); v.y *= gelu_erf_f(g.y); v.z *= gelu_erf_f(g.z); v.w *= gelu_erf_f(g.w); }
+                        v.x *= gelu_erf_f(g.x); v.y *= gelu_erf_f(g.y); v.z *= gelu_erf_f(g.z); v.w *= gelu_erf_f(g.w);
                     }
                 }
                 if (p.rowvec) v += rv[j];
@@ -443,8 +394,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
             for (int j = 0; j < WN; ++j) {
                 if (GEGLU && (j & 1)) continue;
                 const int tc = (GEGLU ? 8 * j : 16 * j) + 4 * fgrp;
-                if constexpr (ablate != 8) *reinterpret_cast<u32x2_t*>(slab + frow * RB + tc * 2) = packed[j];
-                else if (packed[j].x == 0x12345u) bias_lds[lane] = 1.f;
+                *reinterpret_cast<u32x2_t*>(slab + frow * RB + tc * 2) = packed[j];
             }
             // (same wave wrote the slab: LDS executes a wave's instructions in order, no barrier needed — but the COMPILER
             //  must not move the differently-typed reads above the writes, nor the next group's writes above these reads)
@@ -462,12 +412,11 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
                 const int unit = lane + 64 * r;
                 const int rr = unit / UW, u = unit - rr * UW;
                 vout[r] = u32x4_t{0u, 0u, 0u, 0u};
-                if constexpr (ablate != 8) { if (unit < NU) vout[r] = *reinterpret_cast<const u32x4_t*>(slab + rr * RB + u * 16); }
-                else vout[r].x = (uint32_t)i;
+                if (unit < NU) vout[r] = *reinterpret_cast<const u32x4_t*>(slab + rr * RB + u * 16);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_sched_barrier(0);
-            // Store-data discipline (found with gemm_sglds.hip, where 168 registers make the allocator reuse registers at
+            // Store-data discipline (found with the retired wave-specialised kernel, where 168 registers make the allocator reuse registers at
             // once): an LDS read that RETURNS into a pending buffer_store's data registers corrupts the store when the store
             // path is backed up.  So store data is always a VALU-written copy (`sd`), never an LDS-read destination, and the
             // previous group's `sd` is kept alive (fake use) until this group's LDS reads — bias strip, slab — have returned.
@@ -500,11 +449,8 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
             }
             asm volatile("" ::: "memory");
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                if constexpr (ablate != 7)
-                    __builtin_amdgcn_raw_buffer_store_b128(sd[r], out_rsrc, unit_offsets(m0, n0, i, r, p.ldo, geglu_tag), sb, 0);
-                else if (sd[r].x == 0x12345u) bias_lds[lane] = 1.f;          // (keep the value alive)
-            }
+            for (int r = 0; r < NR; ++r)
+                __builtin_amdgcn_raw_buffer_store_b128(sd[r], out_rsrc, unit_offsets(m0, n0, i, r, p.ldo, geglu_tag), sb, 0);
 #pragma unroll
             for (int r = 0; r < NR; ++r) sd_prev[r] = sd[r];
             asm volatile("" ::: "memory");
@@ -523,19 +469,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
     int st = 0;                       // ring slot of the next chunk to consume
     bool first = true;
     elem8_t a0[WM], w0[WN], a1[WM], w1[WN];
-    bool pending = false;             // IL: the second half of a chunk's pieces is still to be issued
-    ChunkCtx cx = chunk_ctx();
-    // ablate == 4 (experiments): block 0, wave 0 stamps s_memtime at {tile start, main loop done, epilogue start, epilogue
-    // end} into p.workspace (uint64 x 4 per tile)
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(p.workspace);
-    int tile_no = 0;
-    auto stamp = [&](int k) {
-        if constexpr (ablate == 4 || ablate == 7 || ablate == 8) {
-            if (bid == 0 && tid == 0 && stamps) stamps[tile_no * 4 + k] = __builtin_readcyclecounter();
-        }
-    };
     for (int item = bid; item < nitems; item += G) {
-        stamp(0);
         // ---- tile prologue: chunk `consumed` must be visible to every wave
         if (first) {
             if (pro == 3) wait_vmcnt<(S == 3 ? 2 : 0) * Cfg::LPT>(); else if (pro == 2) wait_vmcnt<Cfg::LPT>(); else wait_vmcnt<0>();
@@ -544,7 +478,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         __builtin_amdgcn_s_barrier();             // also: every wave has left the previous epilogue's slab
         asm volatile("" ::: "memory");
         if (!Cfg::DEDICATED && !first && issued < total) { issue_one(); ++issued; }   // the refill that the epilogue's slab delayed
-        if constexpr (ablate != 1) read_frags(st, 0, a0, w0);
+        read_frags(st, 0, a0, w0);
         if (!first) {                             // the previous tile's last store data stays alive until these reads returned
             __builtin_amdgcn_s_waitcnt(0xc07f);
 #pragma unroll
@@ -556,40 +490,10 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         const int younger_stores = (!first && S == 2 && staged) ? WM * (geglu ? (16 * WN + 63) / 64 : (32 * WN + 63) / 64) : 0;
         int m0, n0;
         item_tile(item, m0, n0);
-        if constexpr (IL) {
-            constexpr int H0 = Cfg::LPT / 2;
-            using QA = std::integral_constant<int, 0>;
-            using QB = std::integral_constant<int, H0>;
-            using QC = std::integral_constant<int, Cfg::LPT>;
-            for (int t = 0; t + 1 < total_steps; ++t) {
-                phase(a0, w0, a1, w1, st, 1, pending, cx, QB{}, QC{});           // + second half of the chunk in flight
-                if (pending) { advance_chunk(); ++issued; pending = false; }
-                const int stn = st + 1 == S ? 0 : st + 1;
-                if (!known_landed) {
-                    if (issued - consumed >= 3) wait_vmcnt<Cfg::LPT>(); else wait_vmcnt<0>();
-                }
-                known_landed = false;
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                __builtin_amdgcn_s_barrier();         // slot st is free, chunk consumed+1 is visible
-                asm volatile("" ::: "memory");
-                pending = issued < total;
-                if (pending) cx = chunk_ctx();
-                phase(a1, w1, a0, w0, stn, 0, pending, cx, QA{}, QB{});          // + first half of the next refill
-                st = stn;
-                ++consumed;
-            }
-            if (pending) {                            // tile boundary: the rest of the refill goes out in one piece
-#pragma unroll
-                for (int q = H0; q < Cfg::LPT; ++q) issue_piece(cx, q);
-                advance_chunk(); ++issued; pending = false;
-            }
-        } else
         for (int t = 0; t + 1 < total_steps; ++t) {
-            if constexpr (ablate != 1) {
-                read_frags(st, 1, a1, w1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a0, w0);
-            }
+            read_frags(st, 1, a1, w1);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a0, w0);
             const int stn = st + 1 == S ? 0 : st + 1;
             if (!known_landed) {                  // chunk consumed+1 landed (mine); one younger chunk may stay in flight
                 if (S == 3 && issued - consumed >= 3) wait_vmcnt<(S == 3 ? 1 : 0) * Cfg::LPT>();
@@ -600,12 +504,10 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();         // slot st is free, chunk consumed+1 is visible
             asm volatile("" ::: "memory");
-            if constexpr (ablate != 1) {
-                read_frags(stn, 0, a0, w0);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a1, w1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            read_frags(stn, 0, a0, w0);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a1, w1);
+            __builtin_amdgcn_sched_barrier(0);
             if (issued < total) { issue_one(); ++issued; }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             st = stn;
@@ -616,13 +518,10 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         asm volatile("" ::: "memory");
         if (geglu) epilogue_prefetch(m0, n0, std::true_type{}); else epilogue_prefetch(m0, n0, std::false_type{});
         asm volatile("" ::: "memory");
-        if constexpr (ablate != 1) {              // last chunk of the tile
-            read_frags(st, 1, a1, w1);
-            mma(a0, w0);
-            mma(a1, w1);
-        }
+        read_frags(st, 1, a1, w1);                // last chunk of the tile
+        mma(a0, w0);
+        mma(a1, w1);
         ++consumed;
-        stamp(1);
         unsigned char* slab_slot = smem + st * Cfg::STAGE_BYTES;
         st = st + 1 == S ? 0 : st + 1;
         // ---- everything in flight (the next tile's first chunks, issued >= 1 MFMA batch ago) lands; then all waves have
@@ -633,12 +532,9 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         asm volatile("" ::: "memory");
         if (Cfg::DEDICATED && issued < total) { issue_one(); ++issued; }     // slabs are outside the ring: refill at once
         asm volatile("" ::: "memory");
-        stamp(2);
         if (geglu) epilogue(m0, n0, slab_slot, std::true_type{}); else epilogue(m0, n0, slab_slot, std::false_type{});
         zero_acc();
         first = false;
-        stamp(3);
-        ++tile_no;
     }
 }
 
@@ -665,57 +561,22 @@ int launch_pglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
         ncu_eff = n & ~7;                            // whole XCD groups: item & 7 == block & 7 in every round
         if (e == hipSuccess) ncu = ncu_eff;
     }
-    static int ablate = -1;
-    if (ablate < 0) { const char* e = getenv("VMV_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
-    static int order_env = -1;
-    if (order_env < 0) { const char* e = getenv("VMV_GEMM_ORDER"); order_env = e ? atoi(e) : 0; }
     const int slots = ncu_eff * (NWM == 4 ? 1 : 2);
     const int G = nitems < slots ? nitems : slots;
     dim3 grid(G, 1, 1);
-    const int order = (order_env == 1 && G == 256 && NWM == 4) ? 1 : 0;       // (the panel map assumes 32 single-block CUs per XCD)
-    static int il_env = -1;
-    if (il_env < 0) { const char* e = getenv("VMV_GEMM_IL"); il_env = e ? atoi(e) : 0; }
-    auto go_il = [&](auto tag, auto il_tag) -> int {
-        constexpr int AB = decltype(tag)::value;
-        constexpr bool IL = decltype(il_tag)::value;
-        static std::atomic<unsigned long long> attr_set{0};
-        if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_pglds_kernel<NWM, WM, WN, AB, IL>), Cfg::LDS_TOTAL)) return rc_attr;
-        VMV_LAUNCH((gemm_pglds_kernel<NWM, WM, WN, AB, IL>), grid, dim3(Cfg::NT), Cfg::LDS_TOTAL, st, p, tiles_n, total_steps,
-                           nitems, order);
-        return VMV_OK;
-    };
-    auto go = [&](auto tag) -> int {
-#if defined(VMV_EXPERIMENTS)
-        if constexpr (NWM == 4) { if (il_env == 1) return go_il(tag, std::true_type{}); }
-#endif
-        return go_il(tag, std::false_type{});
-    };
-    int rc;
     if (vmv_gemm_ln_inline(p)) {               // row statistics in the main loop: the one-block-per-CU configurations only
         if constexpr (NWM == 4) {
             static std::atomic<unsigned long long> attr_set_lns{0};
-            if (const int rc_attr = vmv_lds_attr_once(attr_set_lns, reinterpret_cast<const void*>(&gemm_pglds_kernel<NWM, WM, WN, 0, false, true>), Cfg::LDS_TOTAL)) return rc_attr;
-            VMV_LAUNCH((gemm_pglds_kernel<NWM, WM, WN, 0, false, true>), grid, dim3(Cfg::NT), Cfg::LDS_TOTAL, st, p, tiles_n,
-                               total_steps, nitems, order);
+            if (const int rc_attr = vmv_lds_attr_once(attr_set_lns, reinterpret_cast<const void*>(&gemm_pglds_kernel<NWM, WM, WN, true>), Cfg::LDS_TOTAL)) return rc_attr;
+            VMV_LAUNCH((gemm_pglds_kernel<NWM, WM, WN, true>), grid, dim3(Cfg::NT), Cfg::LDS_TOTAL, st, p, tiles_n, total_steps, nitems);
             return vmv_launch_status();
         } else {
             return VMV_EINVAL;
         }
     }
-#if defined(VMV_EXPERIMENTS)       // (the ablation / stamp instantiations are not in the production library)
-    switch (ablate) {
-        case 1: rc = go(std::integral_constant<int, 1>{}); break;
-        case 2: rc = go(std::integral_constant<int, 2>{}); break;
-        case 3: rc = go(std::integral_constant<int, 3>{}); break;
-        case 4: rc = go(std::integral_constant<int, 4>{}); break;
-        case 7: rc = go(std::integral_constant<int, 7>{}); break;
-        case 8: rc = go(std::integral_constant<int, 8>{}); break;
-        default: rc = go(std::integral_constant<int, 0>{}); break;
-    }
-#else
-    rc = go(std::integral_constant<int, 0>{});
-#endif
-    if (rc != VMV_OK) return rc;
+    static std::atomic<unsigned long long> attr_set{0};
+    if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_pglds_kernel<NWM, WM, WN>), Cfg::LDS_TOTAL)) return rc_attr;
+    VMV_LAUNCH((gemm_pglds_kernel<NWM, WM, WN>), grid, dim3(Cfg::NT), Cfg::LDS_TOTAL, st, p, tiles_n, total_steps, nitems);
     return vmv_launch_status();
 }
 

@@ -20,7 +20,6 @@
 //     no statistics launch, no rowstat traffic, no colsum correction in the epilogue.
 // One barrier per chunk (160 MFMAs per wave); the ring runs two chunks ahead.
 #include "gemm_glds_common.h"
-#include <cstdlib>
 #include <type_traits>
 
 using namespace vmvg;
@@ -60,18 +59,7 @@ VMV_DEV u32x4_t swap16_xz_yw(u32x4_t v) {
 }
 
 constexpr int RS_GEGLU = 1, RS_LN = 2, RS_RES = 4, RS_GN = 8;
-#ifndef VMV_RS_STAGGER
-#define VMV_RS_STAGGER 0        // experiments: 1 = waves 4-7 take the chunk barrier between the MFMAs and the epilogue of a chunk's last pair
-#endif
-#ifndef VMV_RS_RELAX
-#define VMV_RS_RELAX 1          // experiments: 0 = the chunk-end wait lets only the current chunk's stores stay in flight
-#endif
-#ifndef VMV_RS_PFD
-#define VMV_RS_PFD 1            // W-fragment prefetch distance in k-steps (experiments: 1, 2, 3)
-#endif
-#ifndef VMV_RS_ABLATE
-#define VMV_RS_ABLATE 0         // experiments (results are wrong): 1 no stores, 2 GELU -> identity, 3 no MFMAs, 4 no W DMA after the prologue,
-#endif                          // 5 no LayerNorm arithmetic, 6 no W fragment reads, 7 no chunk barriers; 8 = s_memtime stamps (results right)
+constexpr int RS_PFD = 1;       // W-fragment prefetch distance in k-steps
 
 template <int RT, int KS, int MODE>
 __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, const int tiles_m, const int nsplit, const int cols_per_split) {
@@ -100,19 +88,6 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     const int n_begin = ns * cols_per_split;
     const int ncols = (p.N - n_begin) < cols_per_split ? (p.N - n_begin) : cols_per_split;     // W rows of this block: k * CROWS (launcher)
     const int NC = ncols / Cfg::CROWS;
-#if VMV_RS_ABLATE == 8      // experiments: block 0, waves 0 and 4 stamp s_memtime at the phase boundaries into p.workspace
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(p.workspace);
-    int stamp_i = 0;
-    auto stamp = [&]() {
-        if (stamps && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 4) && stamp_i < 256)
-            stamps[(wave == 4 ? 256 : 0) + stamp_i] = __builtin_readcyclecounter();
-        ++stamp_i;
-    };
-#define RS_STAMP() stamp()
-#else
-#define RS_STAMP()
-#endif
-    RS_STAMP();      // 0: kernel start
 
     // ---- the wave's RT x 16 rows of A, whole K range, straight into registers (rows >= M read as zero through the descriptor)
     const VmvGemmSeg& sg = p.seg[0];
@@ -208,7 +183,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     }
 
     // ---- LayerNorm of the resident rows (two-pass, fp32): lanes frow, frow + 16, + 32, + 48 hold the four k-quarters of a row
-    if constexpr (LN && VMV_RS_ABLATE != 5) {
+    if constexpr (LN) {
         const float inv_k = 1.0f / (float)Cfg::K;
 #pragma unroll
         for (int i = 0; i < RT; ++i) {
@@ -263,7 +238,6 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     const float rs = p.res_scale != 0.f ? p.res_scale : 1.f;
     auto row_ok = [&](int i) { return m_wave + 16 * i + frow < p.M; };
 
-    RS_STAMP();      // 1: resident rows loaded (and normalised), DMA issued
     // ---- first chunk (and the bias strip, issued before it) visible to every wave
     if (pro >= 3) wait_vmcnt_rt(2 * P); else if (pro == 2) wait_vmcnt_rt(P); else wait_vmcnt_rt(0);
     __builtin_amdgcn_s_barrier();
@@ -271,7 +245,6 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
 
     // fragment addressing: this lane's rows 16 j + frow have swz = fsw (lane constant); k-slot (4 kk + fgrp) ^ fsw =
     // 4 (kk ^ (fsw >> 2)) + (fgrp ^ (fsw & 3)), so with NB = 2 (4) lane offsets, one per kk mod NB, every read is base + 64 kk
-    RS_STAMP();      // 2: first chunk landed, barrier passed
     const int fsw = KS == 10 ? ((frow >> 1) & 7) : frow;      // swz() of this lane's fragment rows
     constexpr int NB = KS == 10 ? 2 : 4;
     int foff[NB];
@@ -288,17 +261,13 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
         // ablation on the GPU: with the reads removed the kernel runs 36-47 % faster, i.e. one k-step of cover — 8 MFMAs = 128
         // cycles at 64 rows per wave, 64 cycles at 32 — is less than the loaded LDS latency)
         // (the residual variant at 64 rows per wave has no registers left for a second fragment set: it is HBM-bound anyway)
-        constexpr int PFD = (RES && RT == 4) ? 0 : (VMV_RS_PFD);
+        constexpr int PFD = (RES && RT == 4) ? 0 : RS_PFD;
         constexpr int NBUF = PFD + 1;
         u32x4_t w0[NBUF], w1[NBUF];
         auto rd = [&](const int kk, u32x4_t& x0, u32x4_t& x1) {
             const unsigned char* t = tb[kk & (NB - 1)] + 64 * kk;
-#if VMV_RS_ABLATE == 6
-            x0 = u32x4_t{(uint32_t)(uintptr_t)t, 1u, 2u, 3u}; x1 = x0;
-#else
             x0 = *reinterpret_cast<const u32x4_t*>(t);
             x1 = *reinterpret_cast<const u32x4_t*>(t + 16 * RB);
-#endif
         };
 #pragma unroll
         for (int kk = 0; kk < PFD; ++kk) rd(kk, w0[kk % NBUF], w1[kk % NBUF]);
@@ -307,15 +276,11 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
             const int cur = kk % NBUF;
             if (kk + PFD < KS) rd(kk + PFD, w0[(kk + PFD) % NBUF], w1[(kk + PFD) % NBUF]);
             if constexpr (PFD > 0) __builtin_amdgcn_sched_barrier(0);
-#if VMV_RS_ABLATE == 3
-            c0[0].x += __uint_as_float(w0[cur].x ^ a[kk % RT][kk].x); c1[0].x += __uint_as_float(w1[cur].y ^ a[(kk + 1) % RT][kk].y);
-#else
 #pragma unroll
             for (int i = 0; i < RT; ++i) {
                 c0[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w0[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c0[i], 0, 0, 0);
                 c1[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w1[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c1[i], 0, 0, 0);
             }
-#endif
             if constexpr (PFD > 0) __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -327,9 +292,6 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     };
     auto store_pair = [&](const int ocol, const int i, u32x4_t o) {
         o = swap16_xz_yw(o);
-#if VMV_RS_ABLATE == 1
-        if (o.x == 0x12345u && o.y == 0x54321u)
-#endif
         __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, row_ok(i) ? ovo : OOB, (uint32_t)((m_wave + 16 * i) * p.ldo + ocol) * 2u, 0);
         // Store-data discipline (cf. gemm_pglds.hip): the allocator hands the store's registers to the next row tile's
         // v_pk_add_f32 at once, and with the VALU write directly behind the store the LAST dword of the last four lanes of
@@ -344,31 +306,15 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     auto chunk_end = [&](const int stores) {       // the wave's stores issued behind chunk c + 2's DMA (or a lower bound)
         if (c + 1 < NC) {
             // chunk c + 1 landed (mine): everything issued after its DMA — chunk c + 2's DMA and this chunk's stores — may stay in flight
-#if VMV_RS_ABLATE == 4 || VMV_RS_ABLATE == 1
-            wait_vmcnt_rt(0);
-#else
             wait_vmcnt_rt((c + 2 < NC ? P : 0) + stores);
-#endif
             __builtin_amdgcn_s_waitcnt(0xc07f);
-#if VMV_RS_ABLATE != 7
             __builtin_amdgcn_s_barrier();          // every wave is done with slot `slot`, chunk c + 1 is visible
-#endif
             asm volatile("" ::: "memory");
-#if VMV_RS_ABLATE != 4
             if (c + Cfg::STAGES < NC) issue_chunk(c + Cfg::STAGES, slot);
-#endif
         }
         ++c;
         slot = slot + 1 == Cfg::STAGES ? 0 : slot + 1;
     };
-    // Staggered halves.  All eight waves meet at the chunk barrier, so left alone the two waves of a SIMD (w and w + 4) run in
-    // lock-step: both multiply, then both run their epilogues with the matrix pipe idle (first GPU run: 8.8 k cycles per body of
-    // 2 x 2.56 k MFMA cycles).  Waves 4-7 therefore take the barrier BETWEEN the MFMAs and the epilogue of a chunk's last pair
-    // (their accumulators simply stay live across it): after every barrier one wave of the SIMD starts multiplying while the
-    // other starts an epilogue, and they keep alternating.  The wait count of the late half names the stores that sit behind
-    // the next chunk's DMA at that point (a smaller count than the true one only waits for more).
-    constexpr bool STAGGER = VMV_RS_STAGGER != 0 && !RES;
-    const bool late = STAGGER && wave >= Cfg::NW / 2;
     for (int b = 0; b < nbody; ++b) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -379,23 +325,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
             f32x4_t c0[RT], c1[RT];
             u32x4_t rv[RT];
             if constexpr (RES) load_res(ocol, rv);
-            RS_STAMP();      // 3 + 6 k (+ 3 for h = 1): pair start
             mma_pair(sbase, q, c0, c1);
-            RS_STAMP();      // MFMAs issued
             const bool cend = G == 2 || h == 1;                   // last pair of its chunk (compile-time after unrolling)
             constexpr int SP = GEGLU ? RT / 2 : RT;               // store instructions per pair
-            // chunk_end(n): n = this wave's stores issued since chunk c + 1's DMA went out (at the chunk_end two chunks ago); they and
-            // chunk c + 2's DMA may stay in flight.  (The first version waited for all but the last chunk's stores: with the
-            // write path of a store-heavy GEMM backed up that is a write round trip on the critical path of every chunk.)
-            if (cend && late) {
-#if VMV_RS_RELAX
-                if (G == 4) chunk_end(c == 0 ? SP : c == 1 ? 3 * SP : 4 * SP);
-                else chunk_end(c == 0 ? 0 : c == 1 ? SP : 2 * SP);
-#else
-                if (G == 4) chunk_end(c == 0 ? SP : 2 * SP);
-                else chunk_end(c == 0 ? 0 : SP);
-#endif
-            }
             const f32x4_t b0 = *reinterpret_cast<const f32x4_t*>(bias_lds + nrel + 4 * fgrp);
             const f32x4_t b1 = *reinterpret_cast<const f32x4_t*>(bias_lds + nrel + 16 + 4 * fgrp);
             if constexpr (GEGLU) {
@@ -404,18 +336,11 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
                 for (int i = 0; i < RT; ++i) {
                     f32x4_t v = c0[i] + b0;
                     const f32x4_t gt = c1[i] + b1;
-#if VMV_RS_ABLATE == 2
-                    v *= gt;
-#else
                     v.x *= gelu_erf_f(gt.x); v.y *= gelu_erf_f(gt.y); v.z *= gelu_erf_f(gt.z); v.w *= gelu_erf_f(gt.w);
-#endif
                     hp[i].x = pack_elem2(v.x, v.y); hp[i].y = pack_elem2(v.z, v.w);
                     if (i & 1) {
                         u32x4_t o = swap16_xz_yw(u32x4_t{hp[i - 1].x, hp[i - 1].y, hp[i].x, hp[i].y});
                         const bool ok = m_wave + 16 * (i - 1 + (fgrp & 1)) + frow < p.M;
-#if VMV_RS_ABLATE == 1
-                        if (o.x == 0x12345u && o.y == 0x54321u)
-#endif
                         __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, ok ? ovo_g : OOB, (uint32_t)((m_wave + 16 * (i - 1)) * p.ldo + ocol) * 2u, 0);
                         asm volatile("s_nop 7" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w) : "memory");       // (store-data discipline: store_pair)
                     }
@@ -437,24 +362,15 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
                     store_pair(ocol, i, o);
                 }
             }
-            RS_STAMP();      // epilogue issued
-#if VMV_RS_RELAX
-            if (cend && !late) chunk_end(c == 0 ? SP * (G / 2) : 2 * SP * (G / 2));
-#else
-            if (cend && !late) chunk_end(SP * (G / 2));
-#endif
+            // chunk_end(n): n = this wave's stores issued since chunk c + 1's DMA went out (at the chunk_end two chunks ago); they and
+            // chunk c + 2's DMA may stay in flight.  (The first version waited for all but the last chunk's stores: with the
+            // write path of a store-heavy GEMM backed up that is a write round trip on the critical path of every chunk.)
+            if (cend) chunk_end(c == 0 ? SP * (G / 2) : 2 * SP * (G / 2));
         }
     }
 }
 
 struct RsPlan { int rt, nsplit, cols; };
-
-int rs_policy() {
-    // VMV_GEMM_RS (A/B experiments): 1 (default) = this kernel takes the eligible linears, 0 = off
-    static int pol = -1;
-    if (pol < 0) { const char* e = getenv("VMV_GEMM_RS"); pol = e ? atoi(e) : 1; }
-    return pol;
-}
 
 int ncu_whole_xcds() {
     static int ncu = 0;
@@ -473,15 +389,12 @@ bool rs_plan(const VmvGemmParams& p, int force_rt, RsPlan& best, int ncu) {
     const int K = p.ktot;
     bool found = false;
     double best_cost = 0;
-    static int ns_env = -1;
-    if (ns_env < 0) { const char* e = getenv("VMV_RS_NSPLIT"); ns_env = e ? atoi(e) : 0; }
     for (int rt = 4; rt >= 2; rt -= 2) {
         if (force_rt && rt != force_rt) continue;
         if ((K == 640 || K == 512) && rt != 2) continue;
         const int bm = 128 * rt;
         const long tm = (p.M + bm - 1) / bm;
         for (int ns = 1; ns <= 8; ns *= 2) {
-            if (ns_env > 0 && ns != ns_env) continue;
             if (p.N % (64 * ns)) continue;
             const int cols = p.N / ns;
             if (cols > 5120) continue;
@@ -550,7 +463,7 @@ bool vmv_gemm_rs_supported(const VmvGemmParams& p) {
 
 // policy: the eligible linears with enough rows to fill the chip (the UNet's two large levels)
 bool vmv_gemm_rs_preferred(const VmvGemmParams& p) {
-    if (!rs_policy() || !vmv_gemm_rs_supported(p)) return false;
+    if (!vmv_gemm_rs_supported(p)) return false;
     RsPlan pl;
     if (!rs_plan(p, 0, pl, 256)) return false;
     const long blocks = (long)((p.M + 128 * pl.rt - 1) / (128 * pl.rt)) * pl.nsplit;

@@ -24,7 +24,6 @@
 // into the other A buffer, are old enough to be covered by the ring's own counted wait at phase 6 a + 2, are normalised in place by the
 // lane that fetched them during the MFMAs of phases 6 a + 2 .. 6 a + 4, and become visible with the barrier of phase 6 a + 5.
 #include "gemm_glds_common.h"
-#include <cstdlib>
 #include <type_traits>
 
 using namespace vmvg;
@@ -48,10 +47,6 @@ constexpr int TF_ROWB = TF_BN * 2 + 16;                          // epilogue sta
 static_assert(TF_ROWS * TF_ROWB <= TF_OFF_TAB && TF_LDS <= 160 * 1024, "LDS budget");
 constexpr int TF_WM = 3, TF_WN = 10, TF_WH = 5;  // accumulator tiles per wave: 3 row fragments x 10 column tiles, in two halves of 5
 constexpr int TF_NWI = 2, TF_NWX = 4;            // W wave-instructions per wave per stage: 2, + 1 for waves < 4 (20 groups of 16 rows)
-
-#ifndef VMV_TFR_SGB
-#define VMV_TFR_SGB 0      // experiments: 1 = pin "1 MFMA : 2 VALU" with sched_group_barrier in the half-phases that carry an A half-unit
-#endif
 
 template <bool GN>
 __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p, const int tiles_g, const int tiles_n, const int PT) {
@@ -329,13 +324,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
     }
 }
 
-int tfr_policy() {
-    // VMV_GEMM_TFR (A/B experiments): 1 (default) = this kernel takes the eligible temporal convolutions, 0 = off
-    static int pol = -1;
-    if (pol < 0) { const char* e = getenv("VMV_GEMM_TFR"); pol = e ? atoi(e) : 1; }
-    return pol;
-}
-
 }  // namespace
 
 // host logic: can the frame-resident kernel serve *p at all (forced tile or policy)?
@@ -357,18 +345,16 @@ bool vmv_gemm_tfr_supported(const VmvGemmParams& p) {
 }
 
 // policy: taken when its tiles (samples x pixel groups x N / 320) fill WHOLE rounds of the 256 CUs — >= 200 tiles and >= 95 % of the
-// last round.  Measured (tools/experiments/tfr_bench.py, profiles/r5_tfr_bench.log): a tile runs at the same ~3.4 TFLOP/s per CU as the
+// last round.  Measured (profiles/r5_tfr_bench.log): a tile runs at the same ~3.4 TFLOP/s per CU as the
 // 256 x 320 tile of gemm_xglds.hip, so the frame-resident form wins where its grid quantises better — the first level at 24 x 32 x 32:
 // 256 tiles = one round, 36-39 us against 43 us, folded norm 62-67 us against 74 us for statistics + apply + convolution — and loses
 // where it does not: 24 x 40 x 64 has 640 tiles = 2.5 rounds (100-111 us against 90-94 us).
 bool vmv_gemm_tfr_preferred(const VmvGemmParams& p) {
-    if (!tfr_policy() || !vmv_gemm_tfr_supported(p)) return false;
+    if (!vmv_gemm_tfr_supported(p)) return false;
     const int PT = TF_ROWS / p.F;
     const long tiles = (long)(p.M / ((long)p.F * p.P)) * ((p.P + PT - 1) / PT) * (p.N / TF_BN);
     const long rounds = (tiles + 255) / 256;
-    static double fill_min = -1.0;
-    if (fill_min < 0.0) { const char* e = getenv("VMV_TFR_FILL"); fill_min = e ? atof(e) : 0.95; }      // (A/B experiments)
-    return tiles >= 200 && (double)tiles / (double)(rounds * 256) >= fill_min;
+    return tiles >= 200 && (double)tiles / (double)(rounds * 256) >= 0.95;
 }
 
 int vmv_gemm_tfr_launch(const VmvGemmParams& p, hipStream_t st) {

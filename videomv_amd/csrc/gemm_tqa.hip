@@ -387,13 +387,6 @@ int tqa_ncu() {          // CUs of whole XCDs (one block per CU; gemm_rs.hip ncu
     return ncu;
 }
 
-int tqa_policy() {
-    // VMV_GEMM_TQA (A/B experiments): 1 (default) = the engine records the fused launch where it is supported, 0 = the two-kernel form
-    static int pol = -1;
-    if (pol < 0) { const char* e = getenv("VMV_GEMM_TQA"); pol = e ? atoi(e) : 1; }
-    return pol;
-}
-
 }  // namespace
 
 // host logic: can the fused kernel serve *p?  (VMV_EPI_TATTN has no other home: vmv_gemm returns VMV_EINVAL when this says no)
@@ -415,11 +408,11 @@ bool vmv_gemm_tqa_supported(const VmvGemmParams& p) {
 // (tools/experiments/tqa_bench.py, profiles/r6_tqa_bench.log): 102 us against 167 us for the two launches at the first level of
 // 24 x 40 x 64, 46 against 71 at 24 x 32 x 32, 24 against 54 on rank 0 of 8 (40 row tiles x 5 heads = 200 items).
 bool vmv_gemm_tqa_preferred(const VmvGemmParams& p) {
-    if (!tqa_policy() || !vmv_gemm_tqa_supported(p)) return false;
+    if (!vmv_gemm_tqa_supported(p)) return false;
     const long npix = (long)(p.M / ((long)p.F * p.P)) * p.P;
     const long tiles = (npix + TQ_NW * (TQ_ROWS / p.F) - 1) / (TQ_NW * (TQ_ROWS / p.F));
     static long min_items = -1;
-    if (min_items < 0) { const char* e = getenv("VMV_TQA_MIN_ITEMS"); min_items = e ? atol(e) : 128; }      // (tests / A/B experiments)
+    if (min_items < 0) { const char* e = getenv("VMV_TQA_MIN_ITEMS"); min_items = e ? atol(e) : 128; }      // (tests reach the kernel at small shapes)
     return tiles * (p.N / 192) >= min_items;
 }
 

@@ -17,45 +17,30 @@
 // GEGLU (x | gate column tiles are adjacent accumulators of one lane) — for the K = 1280 level, where the row-stationary kernel does
 // not apply (rows do not fit registers) and the 256 x 128 persistent tiles ran at 780-870 TFLOP/s against 1050-1100 for this one
 // (hipBLASLt on the same box: 1090-1130, profiles/r4_vendor_yardstick.tsv).
-// (tools/experiments/gemm_wglds.hip is the 4-wave / 512-register sibling that lost to LDS-DMA issue stalls.)
+// (A 4-wave / 512-register sibling lost to LDS-DMA issue stalls: DESIGN.md 4.1.)
 #include "gemm_glds_common.h"
-#include <cstdlib>
 #include <type_traits>
 
 using namespace vmvg;
 
 namespace {
 
-#ifndef VMV_XGLDS_VARIANT
-#define VMV_XGLDS_VARIANT 0    // experiments: 1 LDS-DMA issue before the chunk's last MFMA phase, 2 s_setprio 1 around MFMA phases, 3 both
-#endif
-#ifndef VMV_XGLDS_ABLATE
-#define VMV_XGLDS_ABLATE 0     // experiments: 1 no MFMAs, 2 no LDS-DMA after the prologue, 3 no fragment reads, 4 no block barriers
-#endif
 constexpr int WBK = 32;                 // this kernel's K chunk: ONE k-step of v_mfma_f32_16x16x32 (see above)
+constexpr int XG_STAGES = 4;            // ring depth: chunk t + 4 goes out behind the block barrier of step t (see above)
 
 // WNV = the wave grid: 2 = 4 x 2 waves (the 256-row tiles); 1 = 8 x 1 (round 6: a 512 x 128 tile of 64 x 128 wave tiles for the N = 128
 // convolutions of the VAE's first level, whose 64 x 64 wave tiles in every other kernel read 0.5 fragments per MFMA and sit at
-// 670 TFLOP/s whatever the tile: 0.375 here); 4 = 4 x 1 waves in a 256-THREAD block, 256 x 128 tile, three-stage ring (72 KB) and TWO
-// blocks per CU (round 6 experiment for the K = 1280 linears: still 2 waves per SIMD and 64 x 128 wave tiles, but the two blocks of a CU
-// are independent, so one's fill / epilogue runs under the other's main loop — the 14.7 us per 47.6-us tile the one-block form exposes.
-// MEASURED: correct, and slower everywhere — qkv L2 644 vs 754 TFLOP/s, GEGLU L2 756 vs 818, FF-down L2 608 vs 977: a 256 x 128 block
-// moves 50 % more LDS-DMA bytes per flop than the 256 x 256 one and its steady state is DMA-bound at ~620 TFLOP/s; built with
-// EXPERIMENTS=1 only, profiles/r6_y256_bench.log).
+// 670 TFLOP/s whatever the tile: 0.375 here).
 template <int NH, int WH, int WNV = 2>
 struct WgCfg {
     static constexpr int WM = 4, WN = NH * WH;              // 16-row / 16-column MFMA tiles per wave
-    static constexpr int NW = WNV == 4 ? 4 : 8, NT = 64 * NW;          // waves per block: WMV along M x WNW along N
+    static constexpr int NW = 8, NT = 64 * NW;              // waves per block: WMV along M x WNW along N
     static constexpr int WNW = WNV == 2 ? 2 : 1;
     static constexpr int WMV = NW / WNW;
-    static constexpr int BPC = WNV == 4 ? 2 : 1;            // blocks per CU
     static constexpr int BM = 16 * WM * WMV, BN = 16 * WN * WNW;
     static constexpr int A_BYTES = BM * 64, W_BYTES = BN * 64;         // rows of 32 elements = 64 B
     static constexpr int STAGE_BYTES = A_BYTES + W_BYTES;
-#ifndef VMV_XGLDS_STAGES
-#define VMV_XGLDS_STAGES 4      // (experiments: 3 = the depth a persistent form with per-wave epilogue slabs could afford)
-#endif
-    static constexpr int STAGES = WNV == 4 ? 3 : VMV_XGLDS_STAGES;
+    static constexpr int STAGES = XG_STAGES;
     static constexpr int LDS_BYTES = STAGES * STAGE_BYTES;
     static constexpr int NAI = BM / (16 * NW);              // A wave-instructions per wave per chunk (16 rows x 64 B each) = 2 (4 at BM = 512)
     static constexpr int WGROUPS = BN / 16;                 // 16-row groups of W per chunk (20 at BN = 320)
@@ -64,8 +49,8 @@ struct WgCfg {
     static constexpr int LPT = NAI + NWI;                   // loads per lane per chunk (waves < NWX: LPT + 1)
     static constexpr int HALF_ROWS = 128;                   // epilogue staging: 128 rows (two wave rows) at a time
     static constexpr int XG_MAXG = 8;                       // row groups (rowvec rows) one tile's rows may span
-    static_assert(WNV == 1 || WNV == 2 || WNV == 4, "wave grid");
-    static_assert(HALF_ROWS * (BN * 2 + 16) + XG_MAXG * BN * 4 + BN * 4 <= LDS_BYTES && BPC * LDS_BYTES <= 160 * 1024, "LDS budget");
+    static_assert(WNV == 1 || WNV == 2, "wave grid");
+    static_assert(HALF_ROWS * (BN * 2 + 16) + XG_MAXG * BN * 4 + BN * 4 <= LDS_BYTES && LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
 constexpr int XE_GEGLU = 1, XE_LN = 2;       // EPI bits
@@ -75,7 +60,7 @@ constexpr int XE_GEGLU = 1, XE_LN = 2;       // EPI bits
 // p.workspace; gemm_splitk_reduce (gemm.hip) sums the slabs and runs the epilogue.  For the grids that cannot fill the chip with
 // 256-row wide tiles on their own (the fourth UNet level, a frame-parallel rank's M / 8 rows) without falling back to 128-row tiles.
 template <int NH, int WH, int EPI = 0, bool SK = false, int WNV = 2>
-__global__ __launch_bounds__(WNV == 4 ? 256 : 512, WNV == 4 ? 2 : 1) void gemm_xglds_kernel(const VmvGemmParams p, const int tiles_m, const int tiles_n, const int nsteps_arg,
+__global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams p, const int tiles_m, const int tiles_n, const int nsteps_arg,
                                                             const int nsteps_total, const int gm, const int tapmajor) {
     VMV_KERNEL_ENTER();
     using Cfg = WgCfg<NH, WH, WNV>;
@@ -290,30 +275,16 @@ __global__ __launch_bounds__(WNV == 4 ? 256 : 512, WNV == 4 ? 2 : 1) void gemm_x
     auto mma_phase = [&](auto par_tag, auto h_tag) {
         constexpr int par = decltype(par_tag)::value, h = decltype(h_tag)::value;
         constexpr int ws = (par * NH + h) & 1;
-#if VMV_XGLDS_VARIANT >= 2
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int j = 0; j < WH; ++j)
 #pragma unroll
             for (int i = 0; i < WM; ++i)
-#if VMV_XGLDS_ABLATE == 1
-                { if (i == 0 && j == 0) acc[h * WH][0][0] += (float)wf[ws][0][0] + (float)af[par][0][0]; }
-#else
                 acc[h * WH + j][i] = VMV_MFMA16(wf[ws][j], af[par][i], acc[h * WH + j][i], 0, 0, 0);
-#endif
-#if VMV_XGLDS_VARIANT >= 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
     };
     auto prefetch_phase = [&](int slot_idx, auto par_tag, auto h_tag) {     // the fragment reads phase (par, h) needs
         constexpr int par = decltype(par_tag)::value, h = decltype(h_tag)::value;
-#if VMV_XGLDS_ABLATE == 3
-        (void)slot_idx;
-#else
         if constexpr (h == 0) read_a(slot_idx, af[par]);
         read_w(slot_idx, h, wf[(par * NH + h) & 1]);
-#endif
     };
 
     // (the launcher guarantees an even nsteps >= S: the loop body is two chunks, the fragment-set parity a compile-time value)
@@ -347,25 +318,14 @@ __global__ __launch_bounds__(WNV == 4 ? 256 : 512, WNV == 4 ? 2 : 1) void gemm_x
             else if (xw) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 2) * (Cfg::LPT + 1)) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 2) * Cfg::LPT) : "memory");
             __builtin_amdgcn_s_waitcnt(0xc07f);               // my fragment reads of slot st are done
-#if VMV_XGLDS_ABLATE != 4
             __builtin_amdgcn_s_barrier();
-#endif
             asm volatile("" ::: "memory");
             prefetch_phase(stn, P1{}, H0{});
             __builtin_amdgcn_sched_barrier(0);
         }
-#if VMV_XGLDS_VARIANT == 1 || VMV_XGLDS_VARIANT == 3
-        if (issued < nsteps) { issue(st); ++issued; }
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         mma_phase(P0{}, std::integral_constant<int, NH - 1>{});
         __builtin_amdgcn_sched_barrier(0);
-#if VMV_XGLDS_ABLATE == 2
-        ++issued;
-#elif VMV_XGLDS_VARIANT == 1 || VMV_XGLDS_VARIANT == 3
-#else
         if (issued < nsteps) { issue(st); ++issued; }         // chunk t + S into the slot the barrier freed
-#endif
         __builtin_amdgcn_s_waitcnt(0xc07f);
         st = stn;
     };
@@ -527,11 +487,8 @@ __global__ __launch_bounds__(WNV == 4 ? 256 : 512, WNV == 4 ? 2 : 1) void gemm_x
 }
 
 // rows of the tile group that shares W slices in an XCD's L2 (kernel header): minimises the bytes 32 concurrent blocks pull in,
-// gm x BM + 32 / gm x BN per K chunk, with 32 / gm <= the N tiles there are; 1 = the round-5 order.  VMV_XGLDS_GM forces it (A/B).
+// gm x BM + 32 / gm x BN per K chunk, with 32 / gm <= the N tiles there are; 1 = the round-5 order.
 int xglds_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc = 32) {
-    static int env = -2;
-    if (env == -2) { const char* e = getenv("VMV_XGLDS_GM"); env = e ? atoi(e) : -1; }
-    if (env >= 1) return env;
     if (tiles_n < 2 || tiles_m < 2) return 1;
     int best = 1, best_cost = BM + conc * BN;          // conc = blocks an XCD runs at once (32 CUs x blocks per CU)
     for (int gm = 2; gm <= conc; gm *= 2) {
@@ -543,18 +500,12 @@ int xglds_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc = 32) {
     return best;
 }
 
-int xglds_tapmajor() {        // VMV_XGLDS_TAPMAJOR (A/B): 1 = tap-interleaved K walk of the convolutions (kernel header), 0 = segment-major
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VMV_XGLDS_TAPMAJOR"); v = e ? atoi(e) : 1; }
-    return v;
-}
-
 template <int NH, int WH, int EPI = 0, int WNV = 2>
 int launch_xglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     using Cfg = WgCfg<NH, WH, WNV>;
     const int tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
     const int tiles_n = (p.N + Cfg::BN - 1) / Cfg::BN;
-    const int gm = xglds_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, 32 * Cfg::BPC);
+    const int gm = xglds_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN);
     int nsteps = 0;                                          // chunks of WBK = 32 (total_steps counts the other kernels' 64)
     for (int i = 0; i < p.nseg; ++i) nsteps += (p.seg[i].k + WBK - 1) / WBK;
     (void)total_steps;
@@ -577,7 +528,7 @@ int launch_xglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     }
     static std::atomic<unsigned long long> attr_set{0};
     if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_xglds_kernel<NH, WH, EPI, false, WNV>), Cfg::LDS_BYTES)) return rc_attr;
-    VMV_LAUNCH((gemm_xglds_kernel<NH, WH, EPI, false, WNV>), dim3(tiles_m * tiles_n), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, nsteps, nsteps, gm, xglds_tapmajor());
+    VMV_LAUNCH((gemm_xglds_kernel<NH, WH, EPI, false, WNV>), dim3(tiles_m * tiles_n), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, nsteps, nsteps, gm, 1);
     return vmv_launch_status();
 }
 
@@ -587,7 +538,7 @@ int launch_xglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
 int vmv_gemm_xglds_epi_ok(const VmvGemmParams& p, int tile) {
     const bool geglu = p.epilogue == VMV_EPI_GEGLU, lnf = p.rowstat != nullptr;
     if (!geglu && !lnf) return 1;
-    if (tile != VMV_TILE_X256x256 && tile != VMV_TILE_Y256x128) return 0;      // the fused epilogues exist for 64 x 128 wave tiles only
+    if (tile != VMV_TILE_X256x256) return 0;      // the fused epilogues exist for 64 x 128 wave tiles only
     if (lnf && !p.colsum) return 0;
     if (geglu && ((p.N & 31) || p.residual || p.act != VMV_ACT_NONE)) return 0;      // whole x | gate pairs; no residual (as the other kernels)
     return 1;
@@ -608,16 +559,6 @@ int vmv_gemm_xglds_launch(const VmvGemmParams& p, int total_steps, int tile, hip
     const int No = geglu ? p.N / 2 : p.N;
     if (p.ksplit <= 1 && (p.out_fp32 || (p.ldo & 7) || (No & 7) || !vmv_aligned16(p.out) ||
                           (p.residual && ((p.ldr & 7) || !vmv_aligned16(p.residual))))) return VMV_GLDS_UNSUPPORTED;   // staged epilogue only
-    if (tile == VMV_TILE_Y256x128) {          // 4-wave blocks, two per CU (WgCfg WNV = 4): measured and rejected, experiment builds only
-#if defined(VMV_EXPERIMENTS)
-        if (geglu && lnf) return launch_xglds<2, 4, XE_GEGLU | XE_LN, 4>(p, total_steps, st);
-        if (geglu) return launch_xglds<2, 4, XE_GEGLU, 4>(p, total_steps, st);
-        if (lnf) return launch_xglds<2, 4, XE_LN, 4>(p, total_steps, st);
-        return launch_xglds<2, 4, 0, 4>(p, total_steps, st);
-#else
-        return VMV_GLDS_UNSUPPORTED;
-#endif
-    }
     if (geglu || lnf) {
         if (geglu && lnf) return launch_xglds<2, 4, XE_GEGLU | XE_LN>(p, total_steps, st);
         if (geglu) return launch_xglds<2, 4, XE_GEGLU>(p, total_steps, st);

@@ -3,7 +3,6 @@
 // wave-shuffle + LDS reductions; partial sums are written per chunk and reduced in a fixed order, or (long stat groups)
 // added to 64-bit fixed-point integer accumulators — either way results are bitwise reproducible run to run.
 #include "common.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -57,11 +56,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const VmvGroupNormParams 
     const uint16_t* x0 = reinterpret_cast<const uint16_t*>(p.x);
     const uint16_t* x1 = reinterpret_cast<const uint16_t*>(p.x1);
     const int cpg_ = C >> 5;
-#if defined(VMV_GN_ABLATE_PILOT)
-    if (tid < 32) pil[tid] = 0.f;
-#else
     if (tid < 32) pil[tid] = gn_pilot(p, (long)stat * p.rows_per_stat, tid * cpg_);
-#endif
     __syncthreads();
     for (int cs = cl; cs < CS; cs += TPR) {
         float s[8], q[8], pl[8];
@@ -271,19 +266,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const VmvGroupNormParams 
 // they stream in, and normalises from the stage: one launch and one read of x where the general path needs stats (+ fold)
 // + apply — at the small levels those are ~5-9 us of launch latency each for < 10 us of work.  Statistics are two-pass
 // (the data is on chip): mean first, then the squared deviations.  Fixed reduction order: bitwise reproducible.
-#ifndef VMV_GNF_UNROLL
-#define VMV_GNF_UNROLL 4      // (A/B, round 5: 8 / 16 loads in flight per lane measured 1.29 / 1.31 ms per step against 1.28: not the bound.
-                              //  Round 6: the whole slab staged by LDS-DMA — EVERY load of the block in flight before the first wait, one
-                              //  memory round trip instead of seven dependent ones — measured the same again: 16.9 vs 17.4 us per launch in
-                              //  the kernel trace, 47.43 / 47.53 vs 47.54 / 47.35 ms per step (profiles/r6_gnf_dma_step_ab.log), so that form
-                              //  was removed.  A block is ONE wave per SIMD walking four dependent LDS passes: VALU / LDS latency, not memory.)
-#endif
-__global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams p, const int CW, const int stamp) {
+constexpr int GNF_UNR = 4;      // loads in flight per lane.  (Round 5: 8 / 16 measured 1.29 / 1.31 ms per step against 1.28: not the bound.
+                                //  Round 6: the whole slab staged by LDS-DMA — EVERY load of the block in flight before the first wait, one
+                                //  memory round trip instead of seven dependent ones — measured the same again: 16.9 vs 17.4 us per launch in
+                                //  the kernel trace, 47.43 / 47.53 vs 47.54 / 47.35 ms per step (profiles/r6_gnf_dma_step_ab.log), so that form
+                                //  was removed.  A block is ONE wave per SIMD walking four dependent LDS passes: VALU / LDS latency, not memory.)
+__global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams p, const int CW) {
     VMV_KERNEL_ENTER();
-    // stamp != 0 (VMV_GNF_STAMP=1, experiments): block (0, 0) writes s_memtime at its phase edges into p.partial (>= 8 x 8 bytes)
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(p.partial);
-    auto mark = [&](int i) { if (stamp && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) stamps[i] = __builtin_readcyclecounter(); };
-    mark(0);
     extern __shared__ __attribute__((aligned(16))) float sh[];
     const int C = p.C0 + p.C1;
     const int cpg = C >> 5;
@@ -317,7 +306,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
             const long ld = first ? p.ld : p.ld1;
             int r = rl;
             // GNF_UNR loads in flight per lane (more were tried: profiles/r5_gnf_unroll_ab.log)
-            constexpr int GNF_UNR = VMV_GNF_UNROLL;
             for (; r + (GNF_UNR - 1) * RPP < rows; r += GNF_UNR * RPP) {
                 u32x4_t v[GNF_UNR];
 #pragma unroll
@@ -344,7 +332,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
         }
     }
     __syncthreads();
-    mark(1);
     const float n = (float)rows * (float)cpg;
     // (round 6: folding the RPP row lanes with 256 / CW threads per column instead of one measured no gain — the phase is its four
     //  barriers and the shuffle tree, 2 960 vs 2 672 ticks, profiles/r6_gnf_stamps_fold.log)
@@ -367,7 +354,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
         __syncthreads();
     };
     group_totals(s_mean, [&](float s) { return s / n; });
-    mark(2);
     // ---- pass 2 (from the stage): squared deviations from the group mean
     for (int cs = cl; cs < SW; cs += TPR) {
         if (active) {
@@ -385,9 +371,7 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
         }
     }
     __syncthreads();
-    mark(3);
     group_totals(s_rstd, [&](float q) { return rsqrtf(q / n + p.eps); });
-    mark(4);
     for (int c = tid; c < CW; c += 256) {
         const int g = c / cpg;
         const float sc = s_rstd[g] * p.gamma[c0 + c];
@@ -395,7 +379,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
         shift[c] = p.beta[c0 + c] - s_mean[g] * sc;
     }
     __syncthreads();
-    mark(5);
     // ---- apply from the stage
     uint16_t* y = reinterpret_cast<uint16_t*>(p.y);
     if (active) {
@@ -420,7 +403,6 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
             if (p.silu) run(std::true_type{}); else run(std::false_type{});
         }
     }
-    mark(6);
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
@@ -612,10 +594,8 @@ extern "C" int vmv_groupnorm_fused(const VmvGroupNormParams* pp, int32_t cols, v
     static std::atomic<unsigned long long> attr{0};
     if (const int rc_attr = vmv_lds_attr_once(attr, reinterpret_cast<const void*>(&gn_fused_kernel), 160 * 1024)) return rc_attr;
     if (shbytes > 160 * 1024) return VMV_ERANGE;
-    static int stamp_env = -1;
-    if (stamp_env < 0) { const char* e = getenv("VMV_GNF_STAMP"); stamp_env = e ? atoi(e) : 0; }
     hipLaunchKernelGGL(gn_fused_kernel, dim3(C / cols, p.rows / p.rows_per_stat), dim3(256), shbytes,
-                       reinterpret_cast<hipStream_t>(stream), p, cols, stamp_env && pp->partial ? 1 : 0);
+                       reinterpret_cast<hipStream_t>(stream), p, cols);
     return vmv_launch_status();
 }
 

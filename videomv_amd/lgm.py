@@ -237,7 +237,7 @@ class LgmEngine:
         qkv = self.act(x.rows, 3 * C)
         self._gemm(p + ".qkv", x.rows, ops.linear_segs([(hn.ptr, C, C)]), p + ".qkv", qkv)
         ao = self.act(x.rows, C)
-        if hd == 64 or (hd == 32 and os.environ.get("VMV_ATTN_D32", "1") != "0"):
+        if hd == 64 or hd == 32:
             self.rel(hn)                            # flash kernel (head_dim 64, and 32: the 'big' model's 512 / 16 heads)
             m = lambda: ops.seq_map(T * 3 * C, 0, 3 * C, inner=1)
             self.S.attention(ops.attn_params(qkv.ptr, qkv.ptr + 2 * C, qkv.ptr + 4 * C, ao.ptr, m(), m(), m(),

@@ -250,11 +250,6 @@ class UNetEngine:
         # Opt-in: 383 us against 379 us for the two gemm_rs launches inside a step (51.61 / 51.52 ms, same box) — see the
         # kernel's header for why (one 1-KB LDS fragment per MFMA)
         self.ff_fused = os.environ.get("VMV_FF_FUSED", "0") == "1" and self.fold_ln
-        # VMV_GN_FOLD (default 1): the transformers' GroupNorm -> proj_in with the apply pass folded into the GEMM (_gn_folded_proj_in)
-        self.gn_fold = os.environ.get("VMV_GN_FOLD", "1") != "0"
-        # VMV_TCONV_FOLD (default 1): the temporal conv block's GroupNorm -> SiLU -> (3,1,1) conv with the apply pass folded into the
-        # frame-resident kernel's A path (_tconv_folded, csrc/gemm_tfr.hip) wherever that kernel's tiles fill the chip
-        self.tconv_fold = os.environ.get("VMV_TCONV_FOLD", "1") != "0"
         # VMV_TQA (default 1): the TemporalTransformers' q | k | v projection + attention over the frames as ONE launch (csrc/gemm_tqa.hip,
         # VMV_EPI_TATTN) wherever the library serves the shape (K = 320: the first level) — q, k, v never reach memory
         self.tqa = os.environ.get("VMV_TQA", "1") != "0"
@@ -504,8 +499,8 @@ class UNetEngine:
         pass folded into the GEMM (the row-stationary kernel scales / shifts its resident rows from a per-(stat group, channel)
         table, vmv.h gn_table): statistics + a one-block-per-group table launch instead of statistics + a read-modify-write of
         the whole tensor; the GEMM multiplies the values the apply pass would have stored.  The two large levels only (K = 320 /
-        640); VMV_GN_FOLD=0 disables; not on the frame-parallel plans (their totals are gathered between the two launches)."""
-        if not self.gn_fold or self.comm is not None or rps < 512 or rps % 16:
+        640); not on the frame-parallel plans (their totals are gathered between the two launches)."""
+        if self.comm is not None or rps < 512 or rps % 16:
             return False
         Cc = x.C
         nstat = T // rps
@@ -539,8 +534,6 @@ class UNetEngine:
         vmv_groupnorm_apply would have stored.  The normalised tensor is never written or re-read.  Taken where the library's policy
         runs the convolution on that kernel (vmv_gemm_tfr_ok: its tiles fill the chip — the first level at 24 x 40 x 64 and
         24 x 32 x 32); frame-parallel plans gather their totals between the statistics and the table launch as before."""
-        if not self.tconv_fold:
-            return False
         Cc = cur.C
         nstat = T // rps
         W = self.w[f"{q}.weight"]
@@ -576,7 +569,7 @@ class UNetEngine:
     def _collective(self, kind, recv_t: torch.Tensor, send_t: torch.Tensor, label: str):
         """One collective of the frame-sharded plan.  With a VmvComm handle under the communicator (RCCL, or the simulated peers of
         bench.py --simulate-rank) it is RECORDED as a plan op and issued by the C replay loop on the replay's stream; otherwise (gloo
-        on CPU, host-staged debugging, VMV_COMM_NATIVE=0) the plan is cut here and Python issues it between two segments."""
+        on CPU, host-staged debugging) the plan is cut here and Python issues it between two segments."""
         h = getattr(self.comm, "handle", None)
         if h:
             nb = send_t.numel() * send_t.element_size()

@@ -15,7 +15,6 @@ v-prediction x0 (``lgm_vpred``); only its training-time form (``x0 is not None``
 import math
 from typing import Dict
 
-import os
 
 import torch
 import torch.nn as nn
@@ -200,7 +199,7 @@ class UNetSD_I2VGen(nn.Module, LgmMixin):
         self._front.clear()
 
     def _get(self, B, F, H, W, L, device, n_t, share_prefix=False):
-        share_prefix = bool(share_prefix) and os.environ.get("VMV_SHARE_PREFIX", "1") != "0"
+        share_prefix = bool(share_prefix)
         key = (B, F, H, W, L, str(device), n_t, share_prefix)
         if key not in self._engines:
             sd = {k: v.detach() for k, v in self.state_dict().items()}

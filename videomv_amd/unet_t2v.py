@@ -214,7 +214,7 @@ class UNetSD_T2VBase(nn.Module, LgmMixin):
     def engine_for(self, B, F, H, W, L, device, n_t=1, taps=None, share_prefix=False) -> UNetEngine:
         """F = frames of the whole sample.  share_prefix: the B = 2 branches are a CFG pair with identical x_t / t / camera /
         fps (UNetEngine.__init__)."""
-        share_prefix = bool(share_prefix) and os.environ.get("VMV_SHARE_PREFIX", "1") != "0"
+        share_prefix = bool(share_prefix)
         key = (B, F, H, W, L, str(device), n_t, taps is not None, share_prefix)
         eng = self._engines.get(key)
         if eng is None:
