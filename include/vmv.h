@@ -44,7 +44,7 @@ int vmv_elem_type(void);
 int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
- * 103 = VmvGsParams, 104 = VmvGsBatchParams */
+ * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams */
 int vmv_sizeof(int which);
 /* human-readable text for a code returned by any launcher (VMV_E* or hipError_t) */
 const char* vmv_error_string(int code);
@@ -514,6 +514,57 @@ int vmv_gs_batch_key_bits(int n_views, int size);
 int vmv_gs_batch_workspace_bytes(int n_view_gaussians, int n_instances, int key_bits, size_t* scan_bytes, size_t* sort_bytes);
 int vmv_gs_batch_preprocess(const VmvGsBatchParams* p, void* stream);
 int vmv_gs_batch_render(const VmvGsBatchParams* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Fitting Gaussians to a view set (videomv_amd/gs_fit.py): the batched pass above, differentiated.  fp32 throughout.
+ * Per iteration, on one stream:
+ *   vmv_gs_batch_preprocess(&p.pass)             as above; the host reads num_rendered and sizes keys / vals / sort_temp
+ *   vmv_gs_batch_render_state(&p)                = vmv_gs_batch_render (same images and alphas, bit for bit) + per pixel the final
+ *                                                  transmittance final_T and n_contrib = the number of the tile's instances, in blend
+ *                                                  order, up to and including the last one the pixel blended (the early-stop point)
+ *   vmv_gs_image_loss(image, target, ...)        MSE, its gradient dL_dimage and the loss (deterministic sum)
+ *   vmv_gs_batch_backward(&p)                    dL_dimage -> grad [B][N][14] in the activated layout of `gaussians`
+ *   vmv_gs_adam_step(&adam)                      raw parameters, moments, activated [B * N][14] for the next iteration's pass
+ * WORKSPACE LIFETIME: everything the pass wrote (preprocess arrays, scan_temp, keys / vals_sorted, ranges, out_color) and final_T /
+ * n_contrib must stay untouched from _render_state to _backward; pass.gaussians / views / view_projs must be the forward's.
+ * vmv_gs_batch_backward zeroes grad2d itself, then: (1) one block per (view, tile) walks the tile's instances BACK TO FRONT in the
+ * forward's order, with the forward's rules (power > 0 skips; alpha = min(0.99, o e^power), no gradient through the cap; alpha < 1/255
+ * skips; output clamp to [0, 1] with no gradient where it clamps; background blended with the final T), sums each instance's 9
+ * screen-space gradients over the tile's pixels on chip and adds them to grad2d with one atomicAdd(float*) per value and instance;
+ * (2) one thread per (view, Gaussian) carries them through the projection, the EWA Jacobian (with its +-1.3 tan clamp), R diag(s^2) R^T
+ * from the raw quaternion, the +0.3 I dilation and the conic inverse to grad_view (plain stores); (3) grad = the sum of grad_view
+ * over the V views of each sample, in view order (deterministic).  grad2d alone holds float-atomic sums (order-dependent last bits).
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+    VmvGsBatchParams pass;       /* the forward pass (its workspace, out_color included, is read by the backward)      */
+    float* final_T;              /* [B * V][size][size]  written by _render_state                                     */
+    int32_t* n_contrib;          /* [B * V][size][size]  written by _render_state                                     */
+    const float* dL_dimage;      /* [B * V][3][size][size]                                                            */
+    float* grad2d;               /* [B * V * N][9] workspace: d xy 2, d conic 3 (the stored conic_opacity[0..2]), d opacity, d rgb 3 */
+    float* grad_view;            /* [B * V * N][14] workspace: per-view gradient in the layout of gaussians            */
+    float* grad;                 /* [B * N][14] output: sum over the V views                                            */
+} VmvGsBackwardParams;
+int vmv_gs_batch_render_state(const VmvGsBackwardParams* p, void* stream);
+int vmv_gs_batch_backward(const VmvGsBackwardParams* p, void* stream);
+/* loss = mean((image - target)^2) over n floats; dL_dimage = 2 (image - target) / n (may be NULL); loss: ONE float on the device.
+ * workspace >= 1024 floats (per-block partial sums, then one block sums them in a fixed order: deterministic). */
+int vmv_gs_image_loss(const float* image, const float* target, long n, float* dL_dimage, float* loss, float* workspace, void* stream);
+/* One fused Adam step (torch.optim.Adam: bias-corrected, no weight decay) on the raw parameters of n Gaussians, one launch:
+ * params [n][14] = xyz raw 3 | opacity logit 1 (sigmoid) | log scale 3 (exp) | quaternion raw 4 (normalised on the way out) |
+ * SH-DC colour f 3 (rgb = 0.28209479 f + 0.5) — the .ply layout of core/gs.py:97-144 in memory order of `gaussians`.
+ * grad [n][14] is the gradient of the ACTIVATED layout (vmv_gs_batch_backward's output); the step applies the activation Jacobians,
+ * updates m, v and params with lr[group] (groups: 0 position, 1 opacity, 2 scale, 3 rotation, 4 colour) and writes the activated
+ * gaussians [n][14].  step = t >= 1 is the 1-based step count of the bias correction; step = 0 only writes gaussians from params. */
+typedef struct {
+    float* params;               /* [n][14] raw */
+    float* m; float* v;          /* [n][14] first / second moments */
+    const float* grad;           /* [n][14] activated-layout gradient (unused when step = 0) */
+    float* gaussians;            /* [n][14] activated output */
+    int32_t n; int32_t step;
+    float lr[5];
+    float beta1, beta2, eps;
+} VmvGsAdamParams;
+int vmv_gs_adam_step(const VmvGsAdamParams* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Block permute-copy (frame-sharded sampling, DESIGN.md §8: packs / unpacks the all-to-all buffers that switch an

@@ -114,6 +114,17 @@ class GsBatchParams(C.Structure):
                 ("sort_temp_bytes", C.c_size_t), ("ranges", C.c_void_p), ("out_color", C.c_void_p), ("out_alpha", C.c_void_p)]
 
 
+class GsBackwardParams(C.Structure):
+    _fields_ = [("pass_", GsBatchParams), ("final_T", C.c_void_p), ("n_contrib", C.c_void_p), ("dL_dimage", C.c_void_p),
+                ("grad2d", C.c_void_p), ("grad_view", C.c_void_p), ("grad", C.c_void_p)]
+
+
+class GsAdamParams(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p), ("gaussians", C.c_void_p),
+                ("n", C.c_int32), ("step", C.c_int32), ("lr", C.c_float * 5), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float)]
+
+
 class CopyParams(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("inner16", C.c_int32), ("ss0", C.c_int64), ("ss1", C.c_int64), ("ss2", C.c_int64)]
@@ -192,6 +203,10 @@ SYMBOLS = {
     "vmv_gs_batch_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vmv_gs_batch_preprocess": (C.c_int, [C.POINTER(GsBatchParams), _P]),
     "vmv_gs_batch_render": (C.c_int, [C.POINTER(GsBatchParams), _P]),
+    "vmv_gs_batch_render_state": (C.c_int, [C.POINTER(GsBackwardParams), _P]),
+    "vmv_gs_batch_backward": (C.c_int, [C.POINTER(GsBackwardParams), _P]),
+    "vmv_gs_image_loss": (C.c_int, [_P, _P, C.c_long, _P, _P, _P, _P]),
+    "vmv_gs_adam_step": (C.c_int, [C.POINTER(GsAdamParams), _P]),
     "vmv_latent_to_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_latent_to_rows_keep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_i2v_temporal_adapter": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
@@ -246,7 +261,7 @@ def load():
     if lib.vmv_elem_type() != (ELEM_F16 if _elem == "f16" else ELEM_BF16):
         raise RuntimeError(f"{LIB_PATH} was built for another element type")
     for which, st in ((OP_GEMM, GemmParams), (OP_GN_STATS, GroupNormParams), (OP_LAYERNORM, LayerNormParams),
-                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
+                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
         if lib.vmv_sizeof(which) != C.sizeof(st):
             raise RuntimeError(f"struct layout drift for {st.__name__}: C {lib.vmv_sizeof(which)} vs ctypes "
                                f"{C.sizeof(st)}")

@@ -56,6 +56,8 @@ extern "C" int vmv_sizeof(int which) {
         case 102: return (int)sizeof(VmvSeqMap);
         case 103: return (int)sizeof(VmvGsParams);
         case 104: return (int)sizeof(VmvGsBatchParams);
+        case 105: return (int)sizeof(VmvGsBackwardParams);
+        case 106: return (int)sizeof(VmvGsAdamParams);
         default: return (int)op_size(which);
     }
 }

@@ -268,10 +268,13 @@ __global__ __launch_bounds__(256) void gs_ranges_kernel(const VmvGsParams p) {
 // the pair's exponents are packed fp32 operations), the
 // per-lane tests are selects, and the loop leaves when every lane of the wave is done.  Same rule as before per pixel: skip power > 0,
 // alpha = min(0.99, opacity e^power), skip alpha < 1/255, stop BEFORE the Gaussian that would take T below 1e-4.
-template <typename Order>
+// STATE (the fitter's forward, vmv_gs_batch_render_state): also write every pixel's final T and the count of the tile's instances up to and
+// including the last one it blended — what the backward pass (raster_bwd.hip) walks.  STATE = false is the production blend, unchanged.
+template <bool STATE = false, typename Order>
 VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const uint32_t lo, const uint32_t hi,
                            const Order order, const float* __restrict__ xy, const float* __restrict__ conic_opacity,
-                           const float* __restrict__ gaussians, float* __restrict__ out_color, float* __restrict__ out_alpha) {
+                           const float* __restrict__ gaussians, float* __restrict__ out_color, float* __restrict__ out_alpha,
+                           float* __restrict__ out_T = nullptr, int32_t* __restrict__ out_count = nullptr) {
     // staged Gaussians, one array per field (+ 2 pad entries): the loop takes them TWO at a time, a field pair is one ds_read_b64 and
     // the falloff exponents of the pair are packed fp32 operations (v_pk_*: 8 for two Gaussians where the one-at-a-time form issued 16)
     __shared__ __attribute__((aligned(16))) float s_x[258], s_y[258], s_A[258], s_B[258], s_C[258], s_l[258], s_o[258], s_r[258], s_g[258], s_b[258];
@@ -280,6 +283,7 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
     const bool inside = px < size && py < size;
     const float fx = (float)px, fy = (float)py;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Wt = 0.f;
+    int32_t last = 0;                          // (STATE only) instances [lo, lo + last) reach this pixel's last blended one
     bool done = !inside;
     constexpr float LOG2E = 1.4426950408889634f;
     constexpr float CULL = -7.9943534f - 0.02f;      // log2(1 / 255) with a margin: the exact alpha test follows for what passes
@@ -315,6 +319,7 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
             const float w = apply ? alpha * T : 0.0f;
             C0 += s_r[k] * w; C1 += s_g[k] * w; C2 += s_b[k] * w; Wt += w;
             T = apply ? tT : T;
+            if constexpr (STATE) last = apply ? (int32_t)(base - lo) + k + 1 : last;
         };
         const f32x2_t fx2 = {fx, fx}, fy2 = {fy, fy};
         for (int k = 0; k < n; k += 2) {       // (entry n of an odd n is a pad or, in a full batch, never read: n = 256 is even)
@@ -340,6 +345,7 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
         out_color[hw + o] = fminf(1.f, fmaxf(0.f, g));
         out_color[2 * hw + o] = fminf(1.f, fmaxf(0.f, b));
         if (out_alpha) out_alpha[o] = Wt;
+        if constexpr (STATE) { out_T[o] = T; out_count[o] = last; }
     }
 }
 
@@ -361,6 +367,19 @@ __global__ __launch_bounds__(256) void gs_render_batch_kernel(const VmvGsBatchPa
     gs_blend_tile(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy + 2 * vo,
                   p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
                   p.out_alpha ? p.out_alpha + hw * vv : nullptr);
+}
+
+// the fitter's forward: the same blend with the per-pixel state of VmvGsBackwardParams
+__global__ __launch_bounds__(256) void gs_render_batch_state_kernel(const VmvGsBatchParams p, float* __restrict__ final_T,
+                                                                    int32_t* __restrict__ n_contrib) {
+    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
+    const int vv = blockIdx.z;
+    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
+    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
+    const uint32_t* vs = p.vals_sorted;
+    gs_blend_tile<true>(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy + 2 * vo,
+                        p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
+                        p.out_alpha ? p.out_alpha + hw * vv : nullptr, final_T + hw * vv, n_contrib + hw * vv);
 }
 
 int gs_check(const VmvGsParams& p) {
@@ -486,7 +505,8 @@ extern "C" int vmv_gs_batch_preprocess(const VmvGsBatchParams* pp, void* stream)
     return vmv_launch_status();
 }
 
-extern "C" int vmv_gs_batch_render(const VmvGsBatchParams* pp, void* stream) {
+namespace {
+int gs_batch_render(const VmvGsBatchParams* pp, float* final_T, int32_t* n_contrib, void* stream) {
     if (!pp) return VMV_ENULL;
     const VmvGsBatchParams& p = *pp;
     int rc = gs_batch_check(p);
@@ -510,6 +530,16 @@ extern "C" int vmv_gs_batch_render(const VmvGsBatchParams* pp, void* stream) {
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(gs_ranges_batch_kernel, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st, p);
     }
-    hipLaunchKernelGGL(gs_render_batch_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p);
+    if (final_T) hipLaunchKernelGGL(gs_render_batch_state_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, final_T, n_contrib);
+    else hipLaunchKernelGGL(gs_render_batch_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p);
     return vmv_launch_status();
+}
+}  // namespace
+
+extern "C" int vmv_gs_batch_render(const VmvGsBatchParams* pp, void* stream) { return gs_batch_render(pp, nullptr, nullptr, stream); }
+
+extern "C" int vmv_gs_batch_render_state(const VmvGsBackwardParams* pp, void* stream) {
+    if (!pp) return VMV_ENULL;
+    if (!pp->final_T || !pp->n_contrib) return VMV_ENULL;
+    return gs_batch_render(&pp->pass, pp->final_T, pp->n_contrib, stream);
 }

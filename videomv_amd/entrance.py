@@ -90,6 +90,7 @@ def worker(gpu, cfg, cfg_update):
     cfg.rank = cfg.pmi_rank
     # frame_parallel (not a reference key; BASELINE configs[2]): the ranks share ONE sample — same seed, F / N views each
     fpar = bool(cfg.get('frame_parallel', False)) and cfg.world_size > 1
+    _check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')) and not (fpar and bool(cfg.get('cfg_parallel', False))))
     torch.manual_seed(cfg.seed if fpar else rank_seed(cfg.seed, cfg.rank))
     on_gpu = str(cfg.device).startswith("cuda")
     device = torch.device("cuda", gpu) if on_gpu else torch.device(cfg.device)
@@ -149,6 +150,7 @@ def worker(gpu, cfg, cfg_update):
     one_only = (use_lgm and (not on_gpu or fpar)) or (fpar and bool(cfg.get('cfg_parallel', False)))
     pbatch = 1 if one_only else max(1, int(cfg.get('prompt_batch', 1) or 1))
     elevation, camera_dist = 15, 2.0
+    gs_exports = []
 
     def run_group(group):
         camera_data = entrance_camera_data(F, elevation=elevation, camera_distance=camera_dist)
@@ -184,6 +186,9 @@ def worker(gpu, cfg, cfg_update):
                 torch.save({'latent': x0_gs.cpu(), 'video': video_gs.cpu(), 'caption': caption}, osp.join(cfg.log_dir, stem + '_gs.pt'))
                 _save_contact_sheet(video_gs.cpu(), osp.join(cfg.log_dir, stem + '_gs.png'), cfg.mean, cfg.std)
                 _save_frames_safe(osp.join(cfg.log_dir, stem + '_gs.mp4'), video_gs, cfg)
+                if cfg.get('save_gaussians'):
+                    gs_exports.append(_export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist,
+                                                        osp.join(cfg.log_dir, stem), device))
             logging.info('Save views to %s' % path)
             outputs.append(path)
 
@@ -211,6 +216,8 @@ def worker(gpu, cfg, cfg_update):
         dist.barrier()
         dist.destroy_process_group()
     cfg.outputs = outputs
+    if cfg.get('save_gaussians'):
+        cfg.gs_exports = gs_exports
     return cfg
 
 
@@ -252,6 +259,7 @@ def worker_i2v(gpu, cfg, cfg_update):
         cfg = AttrDict(assign_signle_cfg(cfg, cfg_update, 'vldm_cfg'))
         merge_into(cfg, _plain(dict(cfg_update)))
     cfg.gpu, cfg.seed, cfg.rank = gpu, int(cfg.seed), cfg.pmi_rank
+    _check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')))
     if cfg.get('hip_dtype'):                        # (not a reference key) 16-bit storage type of the kernels: fp16 | bf16
         from . import _lib
         _lib.set_elem(cfg.hip_dtype)
@@ -297,6 +305,7 @@ def worker_i2v(gpu, cfg, cfg_update):
     # b = 2.  Noises are drawn per image in list order; the LGM-refined second loop is batched too (47 plain steps in one plan, the 3
     # refined ones sample by sample: diffusion_ddim.ddim_sample_loop).
     pbatch = 1 if (use_lgm and not on_gpu) else max(1, int(cfg.get('prompt_batch', 1) or 1))
+    gs_exports = []
 
     def run_group(group):
         ys, vis, locs, noises = [], [], [], []
@@ -321,7 +330,7 @@ def worker_i2v(gpu, cfg, cfg_update):
                                             ddim_timesteps=int(cfg.ddim_timesteps), eta=0.0)
         from .pipeline import decode_views
         video_all = decode_views(autoencoder, x0_all, int(cfg.decoder_bs), cfg.scale_factor)
-        x0_gs_all = video_gs_all = None
+        x0_gs_all = video_gs_all = gs_data = None
         if use_lgm:       # second, LGM-refined loop from the same noise (inference_i2vgen_entrance.py:281-292)
             from .lgm import prepare_gs_data
             gs_data = prepare_gs_data(camera_data, model.lgm_opt)
@@ -341,6 +350,9 @@ def worker_i2v(gpu, cfg, cfg_update):
                 torch.save({'latent': x0_gs.cpu(), 'video': video_gs.cpu(), 'image': line}, osp.join(cfg.log_dir, stem + '_gs.pt'))
                 _save_contact_sheet(video_gs.cpu(), osp.join(cfg.log_dir, stem + '_gs.png'), cfg.mean, cfg.std)
                 _save_frames_safe(osp.join(cfg.log_dir, stem + '_gs.mp4'), video_gs, cfg)
+                if cfg.get('save_gaussians'):
+                    gs_exports.append(_export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist,
+                                                        osp.join(cfg.log_dir, stem), device))
             logging.info('Save views to %s' % path)
             outputs.append(path)
 
@@ -373,7 +385,65 @@ def worker_i2v(gpu, cfg, cfg_update):
         dist.barrier()
         dist.destroy_process_group()
     cfg.outputs = outputs
+    if cfg.get('save_gaussians'):
+        cfg.gs_exports = gs_exports
     return cfg
+
+
+def _check_export_cfg(cfg, use_lgm):
+    """`save_gaussians` (not a reference key) exports the LGM-refined loop's Gaussians: refuse it, before any sampling, where that loop
+    does not run or cannot run (the LGM renders square views only)."""
+    if not cfg.get('save_gaussians'):
+        return
+    if not use_lgm:
+        raise ValueError("save_gaussians needs the LGM-refined loop: set UNet.use_lgm_refine True (and no cfg_parallel)")
+    if int(cfg.resolution[0]) != int(cfg.resolution[1]):
+        raise ValueError(f"save_gaussians: the LGM branch renders square views, resolution {list(cfg.resolution)} is not square")
+
+
+@torch.no_grad()
+def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist, stem, device):
+    """The 3-D asset of one LGM-refined sample: the LGM on its final key views (LgmRefiner.gaussians_from_views), optionally fitted to
+    all its decoded views (gs_fit.GaussianFitter: targets video * 0.5 + 0.5 against the refiner's background), written as
+    ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit.  Draws nothing from
+    the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
+    from .gs import GaussianRenderer
+    from .lgm import orbit_cameras
+    refiner = model.lgm_refiner(device)
+    opt = refiner.opt
+    F_ = video_gs.shape[2]
+    idxs = [0, 6, 12, 18] if F_ == 24 else [i * F_ // 4 for i in range(4)]
+    views = video_gs[0].permute(1, 0, 2, 3).to(device, torch.float32)                 # [F, 3, H, W] in [-1, 1]
+    g = refiner.gaussians_from_views(views[idxs].contiguous(), gs_data)              # [1, N, 14]
+    rec = dict(ply=stem + '_gs.ply', fit_iters=int(cfg.get('gs_fit_iters') or 0))
+    if rec['fit_iters'] > 0:
+        from .gs_fit import GaussianFitter
+        bg = (refiner.bg_color,) * 3
+        fitter = GaussianFitter(g[0], gs_data['cam_view'][0], gs_data['cam_view_proj'][0], (views * 0.5 + 0.5).contiguous(), bg=bg,
+                                lr_scale=float(cfg.get('gs_fit_lr_scale') or 1.0), fovy=opt.fovy, znear=opt.znear, zfar=opt.zfar)
+        st = fitter.fit(rec['fit_iters'])
+        g = fitter.gaussians().unsqueeze(0)
+        rec.update(st)
+        logging.info(f"gs fit: {rec['fit_iters']} iterations on {F_} views, PSNR {st['psnr_before']:.2f} -> {st['psnr_after']:.2f} dB "
+                     f"(loss {st['loss_before']:.3e} -> {st['loss_after']:.3e}), {st['ms_per_iter']:.2f} ms/iteration, "
+                     f"{st['instances']} instances")
+    rec['vertices'] = refiner.renderer.save_ply(g, rec['ply'])
+    logging.info(f"Save 3D Gaussians ({rec['vertices']} of {g.shape[1]}) to {rec['ply']}")
+    n_orbit = int(cfg.get('gs_orbit_views') or 0)
+    if n_orbit > 0:
+        elev = cfg.get('gs_orbit_elevation')
+        elev = elevation if elev is None else float(elev)
+        size = int(cfg.get('gs_orbit_size') or opt.output_size)
+        cv, cvp = orbit_cameras(camera_data, n_orbit, elev, camera_dist, opt)
+        bgc = torch.full((3,), refiner.bg_color, dtype=torch.float32, device=device)
+        img = GaussianRenderer(size, opt.fovy, opt.znear, opt.zfar).render(g.to(device), cv.to(device), cvp.to(device), None,
+                                                                          bg_color=bgc)["image"]
+        mean, std = torch.tensor(cfg.mean).view(1, 3, 1, 1, 1), torch.tensor(cfg.std).view(1, 3, 1, 1, 1)
+        video = (img.float().cpu().permute(0, 2, 1, 3, 4) - mean) / std                 # [1, 3, n, S, S], the entrance's range
+        rec['orbit_sheet'], rec['orbit_frames'] = stem + '_gs_orbit.png', stem + '_gs_orbit'
+        _save_contact_sheet(video, rec['orbit_sheet'], cfg.mean, cfg.std)
+        _save_frames_safe(stem + '_gs_orbit.mp4', video, cfg)
+    return rec
 
 
 def _save_frames_safe(local_path, video, cfg):

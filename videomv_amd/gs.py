@@ -11,6 +11,7 @@ kernels follow the published forward algorithm (oracle/gs_ref.py, parity unpinne
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -184,3 +185,59 @@ class GaussianRenderer:
                 p.out_color, p.out_alpha = images[b, v].data_ptr(), alphas[b, v].data_ptr()
                 L.check(lib.vmv_gs_render(C.byref(p), _stream_ptr()), "gs_render")
         return {"image": images, "alpha": alphas}
+
+    # ------------------------------------------------------------------ .ply export (core/gs.py:97-186 of the reference)
+    PLY_PROPERTIES = ("x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2",
+                      "rot_0", "rot_1", "rot_2", "rot_3")
+
+    def save_ply(self, gaussians, path, compatible=True):
+        """gaussians [1, N, 14] (activated: pos, opacity, scale, rotation, rgb) -> binary little-endian .ply of the 3-D Gaussian
+        Splatting layout, rows with opacity < 0.005 dropped; ``compatible`` stores the pre-activation values (logit opacity, log
+        scale, SH-DC colour).  Written by hand (the reference uses plyfile).  Returns the number of vertices written."""
+        assert gaussians.shape[0] == 1, 'only support batch size 1'
+        g = gaussians[0].detach().float().cpu()
+        g = g[g[:, 3] >= 0.005]
+        pos, opacity, scales, rots, rgb = g[:, 0:3], g[:, 3:4], g[:, 4:7], g[:, 7:11], g[:, 11:14]
+        if compatible:
+            o = opacity.clamp(1e-6, 1 - 1e-6)                        # kiui.op.inverse_sigmoid
+            opacity = torch.log(o / (1 - o))
+            scales = torch.log(scales + 1e-8)
+            rgb = (rgb - 0.5) / 0.28209479177387814
+        body = torch.cat([pos, rgb, opacity, scales, rots], dim=1).numpy().astype("<f4")
+        header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % body.shape[0]
+        header += "".join("property float %s\n" % n for n in self.PLY_PROPERTIES) + "end_header\n"
+        with open(path, "wb") as f:
+            f.write(header.encode("ascii"))
+            f.write(np.ascontiguousarray(body).tobytes())
+        return int(body.shape[0])
+
+    @classmethod
+    def load_ply(cls, path, compatible=True):
+        """The inverse of ``save_ply`` (any binary little-endian vertex element with float properties that include the 14 names):
+        -> gaussians [N, 14] activated (fp32, CPU)."""
+        with open(path, "rb") as f:
+            data = f.read()
+        end = data.index(b"end_header\n") + len(b"end_header\n")
+        lines = data[:end].decode("ascii").splitlines()
+        if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+            raise ValueError(f"{path}: not a binary little-endian .ply")
+        count, names = None, []
+        for ln in lines[2:]:
+            w = ln.split()
+            if w[0] == "element":
+                if count is not None:
+                    break                                              # (only the first element, the vertices, is read)
+                count = int(w[2])
+            elif w[0] == "property":
+                if w[1] != "float":
+                    raise ValueError(f"{path}: property {ln!r} is not a float")
+                names.append(w[2])
+        rows = np.frombuffer(data, dtype="<f4", count=count * len(names), offset=end).reshape(count, len(names))
+        col = {n: rows[:, i] for i, n in enumerate(names)}
+        order = ("x", "y", "z", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3", "f_dc_0", "f_dc_1", "f_dc_2")
+        g = torch.from_numpy(np.stack([col[n] for n in order], axis=1).astype(np.float32))
+        if compatible:
+            g[:, 3:4] = torch.sigmoid(g[:, 3:4])
+            g[:, 4:7] = torch.exp(g[:, 4:7])
+            g[:, 11:] = 0.28209479177387814 * g[:, 11:] + 0.5
+        return g

@@ -1,0 +1,187 @@
+"""``GaussianFitter`` — fits a fixed set of 3-D Gaussians to a view set on the gfx950 rasteriser and its backward pass
+(``csrc/raster.hip`` + ``csrc/raster_bwd.hip``, contract: ``include/vmv.h`` "Fitting Gaussians to a view set").
+
+The reference's last stage, reconstruction from the generated views, is unreleased (its README lists it as to-do); its LGM trains
+on an image MSE (``core/models.py:169``) and exports with ``save_ply`` (``core/gs.py:97``).  Here the LGM's feed-forward Gaussians
+of the final sample are the starting point and every generated view is a target.  One iteration on one stream: batched preprocess
+-> ONE host read of the instance total -> forward with saved state -> MSE + dL/dimage -> blend backward -> preprocess backward and
+view sum -> fused Adam step on the raw parameters (logit opacity, log scale, raw quaternion, SH-DC colour: the .ply layout), which
+writes the activated Gaussians the next forward reads.  N stays fixed (no densification or pruning).
+"""
+import ctypes as C
+import math
+import time
+
+import torch
+
+from . import _lib as L
+from .gs import GaussianRenderer
+from .ops import _stream_ptr
+
+SH_C0 = 0.28209479177387814
+# per-group learning rates of 3-D Gaussian Splatting (Kerbl et al. 2023, arguments.py: position 1.6e-4 x the scene extent, feature
+# 2.5e-3, opacity 5e-2, scaling 5e-3, rotation 1e-3), the position group multiplied by the extent of the cameras
+DEFAULT_LR = dict(position=1.6e-4, opacity=5e-2, scale=5e-3, rotation=1e-3, colour=2.5e-3)
+
+
+def gaussians_to_raw(g):
+    """activated [..., 14] -> raw parameters of the Adam step (and of the .ply): xyz, logit opacity, log scale, quaternion, SH DC."""
+    g = g.float()
+    o = g[..., 3:4].clamp(1e-6, 1 - 1e-6)
+    return torch.cat([g[..., 0:3], torch.log(o / (1 - o)), torch.log(g[..., 4:7].clamp_min(1e-8)), g[..., 7:11],
+                      (g[..., 11:14] - 0.5) / SH_C0], dim=-1)
+
+
+def psnr(mse):
+    return float("inf") if mse <= 0 else -10.0 * math.log10(mse)
+
+
+class GaussianFitter:
+    """gaussians [N, 14] or [B, N, 14] (activated), cam_view / cam_view_proj [V, 4, 4] or [B, V, 4, 4], targets [V, 3, S, S] or
+    [B, V, 3, S, S] in [0, 1], bg: 3 floats.  ``lr``: dict overriding ``DEFAULT_LR``; ``lr_scale`` multiplies every group."""
+
+    def __init__(self, gaussians, cam_view, cam_view_proj, targets, bg=(0.5, 0.5, 0.5), lr=None, lr_scale=1.0, fovy=39.6,
+                 znear=0.5, zfar=2.5, betas=(0.9, 0.999), eps=1e-15):
+        g = gaussians if gaussians.dim() == 3 else gaussians.unsqueeze(0)
+        cv = cam_view if cam_view.dim() == 4 else cam_view.unsqueeze(0)
+        cvp = cam_view_proj if cam_view_proj.dim() == 4 else cam_view_proj.unsqueeze(0)
+        tg = targets if targets.dim() == 5 else targets.unsqueeze(0)
+        self.device = g.device
+        if self.device.type != "cuda":
+            raise RuntimeError("GaussianFitter runs on the HIP rasteriser: the Gaussians must be on a GPU")
+        self.B, self.N = g.shape[0], g.shape[1]
+        self.V, self.S = cv.shape[1], tg.shape[-1]
+        if cv.shape[0] != self.B or tuple(tg.shape) != (self.B, self.V, 3, self.S, self.S):
+            raise ValueError(f"shapes: gaussians {tuple(g.shape)}, cam_view {tuple(cv.shape)}, targets {tuple(tg.shape)}")
+        self.renderer = GaussianRenderer(self.S, fovy, znear, zfar)
+        self.bg = [float(v) for v in (bg.reshape(-1)[:3] if torch.is_tensor(bg) else bg)]
+        dev = self.device
+        self.views = cv.to(dev, torch.float32).reshape(self.B * self.V, 16).contiguous()
+        self.view_projs = cvp.to(dev, torch.float32).reshape(self.B * self.V, 16).contiguous()
+        self.targets = tg.to(dev, torch.float32).contiguous()
+        # scene extent of 3-D GS (cameras_extent): 1.1 x the largest distance of a camera centre from their mean
+        centres = torch.inverse(cv.detach().cpu().double().transpose(-1, -2))[..., :3, 3].reshape(-1, 3)
+        self.extent = 1.1 * float((centres - centres.mean(0)).norm(dim=1).max()) or 1.0
+        lrs = dict(DEFAULT_LR, **(lr or {}))
+        self.lr = [lrs["position"] * self.extent * lr_scale, lrs["opacity"] * lr_scale, lrs["scale"] * lr_scale,
+                   lrs["rotation"] * lr_scale, lrs["colour"] * lr_scale]
+        self.betas, self.eps = betas, eps
+        n = self.B * self.N
+        self.params = gaussians_to_raw(g.detach()).to(dev).reshape(n, 14).contiguous()
+        self.m, self.v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.gs = torch.empty_like(self.params)
+        self.grad = torch.zeros_like(self.params)
+        self.t = 0
+        VV, S = self.B * self.V, self.S
+        self.image = torch.empty(VV, 3, S, S, dtype=torch.float32, device=dev)
+        self.alpha = torch.empty(VV, 1, S, S, dtype=torch.float32, device=dev)
+        self.final_T = torch.empty(VV, S, S, dtype=torch.float32, device=dev)
+        self.n_contrib = torch.empty(VV, S, S, dtype=torch.int32, device=dev)
+        self.dL = torch.empty_like(self.image)
+        self.grad2d = torch.empty(VV * self.N, 9, dtype=torch.float32, device=dev)
+        self.grad_view = torch.empty(VV * self.N, 14, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.loss_ws = torch.empty(1024, dtype=torch.float32, device=dev)
+        self.num_rendered = 0
+        self._adam(0)                                  # activated Gaussians of the raw parameters (what the first forward reads)
+
+    # ------------------------------------------------------------------ stages
+    def _adam(self, step):
+        a = L.GsAdamParams()
+        a.params, a.m, a.v, a.grad, a.gaussians = (self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grad.data_ptr(),
+                                                   self.gs.data_ptr())
+        a.n, a.step = self.B * self.N, int(step)
+        for i, x in enumerate(self.lr):
+            a.lr[i] = x
+        a.beta1, a.beta2, a.eps = self.betas[0], self.betas[1], self.eps
+        L.check(L.load().vmv_gs_adam_step(C.byref(a), _stream_ptr()), "gs_adam_step")
+
+    def _forward(self):
+        """Preprocess, size the instance buffers (one host read), forward with state.  -> the backward's argument block."""
+        lib, r = L.load(), self.renderer
+        B, V, N, S = self.B, self.V, self.N, self.S
+        buf = r._batch_buffers(B, V, N, self.device)
+        q = L.GsBackwardParams()
+        p = q.pass_
+        p.gaussians, p.B, p.N, p.V, p.size = self.gs.data_ptr(), B, N, V, S
+        p.views, p.view_projs, p.tan_half_fov = self.views.data_ptr(), self.view_projs.data_ptr(), r.tan_half_fov
+        p.bg[0], p.bg[1], p.bg[2] = self.bg
+        p.depth, p.xy, p.conic_opacity, p.rect = buf["depth"].data_ptr(), buf["xy"].data_ptr(), buf["co"].data_ptr(), buf["rect"].data_ptr()
+        p.tiles_touched, p.offsets = buf["touched"].data_ptr(), buf["offsets"].data_ptr()
+        p.scan_temp, p.scan_temp_bytes = buf["scan"].data_ptr(), buf["scan"].numel()
+        L.check(lib.vmv_gs_batch_preprocess(C.byref(p), _stream_ptr()), "gs_batch_preprocess")
+        buf["total"].copy_(buf["offsets"][B * V * N - 1:], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        n = int(buf["total"][0])
+        if n < 0 or n > (1 << 28):
+            raise RuntimeError(f"GaussianFitter: {n} instances — too many for one pass (fewer views or a smaller image)")
+        if n > buf["cap"]:
+            cap = max(int(n * 1.25), 1 << 16)
+            sb, so = C.c_size_t(0), C.c_size_t(0)
+            L.check(lib.vmv_gs_batch_workspace_bytes(B * V * N, cap, buf["bits"], C.byref(sb), C.byref(so)), "gs_batch_workspace_bytes")
+            i64 = lambda: torch.zeros(cap, dtype=torch.int64, device=self.device)
+            i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=self.device)
+            buf.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
+                       sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=self.device))
+        self.num_rendered = p.num_rendered = n
+        if n > 0:
+            p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(), buf["vals"].data_ptr(),
+                                                            buf["vals_s"].data_ptr())
+            p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
+        p.ranges = buf["ranges"].data_ptr()
+        p.out_color, p.out_alpha = self.image.data_ptr(), self.alpha.data_ptr()
+        q.final_T, q.n_contrib = self.final_T.data_ptr(), self.n_contrib.data_ptr()
+        q.dL_dimage, q.grad2d, q.grad_view, q.grad = self.dL.data_ptr(), self.grad2d.data_ptr(), self.grad_view.data_ptr(), self.grad.data_ptr()
+        L.check(lib.vmv_gs_batch_render_state(C.byref(q), _stream_ptr()), "gs_batch_render_state")
+        return q
+
+    def _loss(self, with_grad=True):
+        L.check(L.load().vmv_gs_image_loss(self.image.data_ptr(), self.targets.data_ptr(), self.image.numel(),
+                                           self.dL.data_ptr() if with_grad else None, self.loss.data_ptr(), self.loss_ws.data_ptr(),
+                                           _stream_ptr()), "gs_image_loss")
+
+    def _backward(self, q):
+        L.check(L.load().vmv_gs_batch_backward(C.byref(q), _stream_ptr()), "gs_batch_backward")
+
+    # ------------------------------------------------------------------ public
+    def step(self, events=None):
+        """One iteration.  ``events``: optional list that receives CUDA events after each stage (tools/gs_fit_bench.py)."""
+        mark = (lambda: events.append(torch.cuda.Event(enable_timing=True)) or events[-1].record()) if events is not None else (lambda: None)
+        mark()
+        q = self._forward()
+        mark()
+        self._loss()
+        mark()
+        L.check(L.load().vmv_gs_batch_backward(C.byref(q), _stream_ptr()), "gs_batch_backward")
+        mark()
+        self.t += 1
+        self._adam(self.t)
+        mark()
+
+    def evaluate(self):
+        """-> MSE of the current Gaussians against the targets (forward + loss, no update)."""
+        self._forward()
+        self._loss(with_grad=False)
+        return float(self.loss.item())
+
+    def fit(self, iters):
+        """``iters`` iterations -> dict(loss_before, loss_after, psnr_before, psnr_after, ms_per_iter, iters, instances)."""
+        before = self.evaluate()
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        for _ in range(int(iters)):
+            self.step()
+        torch.cuda.synchronize(self.device)
+        ms = (time.perf_counter() - t0) * 1e3 / max(1, int(iters))
+        after = self.evaluate()
+        return dict(loss_before=before, loss_after=after, psnr_before=psnr(before), psnr_after=psnr(after), ms_per_iter=ms,
+                    iters=int(iters), instances=self.num_rendered)
+
+    def gaussians(self):
+        """activated Gaussians [N, 14] (or [B, N, 14] for B > 1), a copy"""
+        g = self.gs.detach().clone().reshape(self.B, self.N, 14)
+        return g[0] if self.B == 1 else g
+
+    def images(self):
+        """the last forward's renders [B, V, 3, S, S]"""
+        return self.image.reshape(self.B, self.V, 3, self.S, self.S)

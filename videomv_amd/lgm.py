@@ -379,18 +379,34 @@ def prepare_gs_data(camera_data: torch.Tensor, opt: LgmOptions = None) -> dict:
     (tools/inferences/inference_text2video_entrance.py:198-235), conventions included."""
     opt = opt or LgmOptions()
     T = camera_data.shape[1]
-    cam = camera_data.detach().cpu().clone().reshape(T, 4, 4).contiguous().float()
-    cam[:, 1] *= -1
-    cam[:, [1, 2]] = cam[:, [2, 1]]
-    cam[:, :3, 1:3] *= -1
-    dist = float(torch.sqrt(cam[0, 0, 3] ** 2 + cam[0, 1, 3] ** 2 + cam[0, 2, 3] ** 2))
-    transform = torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, dist], [0, 0, 0, 1]], dtype=torch.float32) @ torch.inverse(cam[0])
-    poses = transform.unsqueeze(0) @ cam
+    cam = _gs_cams(camera_data)
+    poses = _gs_transform(cam).unsqueeze(0) @ cam
     rays = []
     for i in range(T):
         o, d = get_rays(poses[i], opt.input_size, opt.input_size, opt.fovy)
         rays.append(torch.cat([torch.cross(o, d, dim=-1), d], dim=-1))
     rays = torch.stack(rays, dim=0).permute(0, 3, 1, 2).contiguous()
+    view, view_proj, cam_pos = _gs_view(poses, opt)
+    return dict(input=rays.unsqueeze(0), cam_view=view.unsqueeze(0), cam_view_proj=view_proj.unsqueeze(0), cam_pos=cam_pos.unsqueeze(0))
+
+
+def _gs_cams(camera_data):
+    """camera_data [1, T, 16] -> the OpenGL camera-to-world matrices [T, 4, 4] of the entrance (:198-205)."""
+    T = camera_data.shape[1]
+    cam = camera_data.detach().cpu().clone().reshape(T, 4, 4).contiguous().float()
+    cam[:, 1] *= -1
+    cam[:, [1, 2]] = cam[:, [2, 1]]
+    cam[:, :3, 1:3] *= -1
+    return cam
+
+
+def _gs_transform(cam):
+    """The normalisation of a view set to its first camera (entrance :206-208): that camera ends up at (0, 0, dist) facing the origin."""
+    dist = float(torch.sqrt(cam[0, 0, 3] ** 2 + cam[0, 1, 3] ** 2 + cam[0, 2, 3] ** 2))
+    return torch.tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, dist], [0, 0, 0, 1]], dtype=torch.float32) @ torch.inverse(cam[0])
+
+
+def _gs_view(poses, opt):
     tan = math.tan(0.5 * math.radians(opt.fovy))
     proj = torch.zeros(4, 4)
     proj[0, 0] = proj[1, 1] = 1 / tan
@@ -400,8 +416,20 @@ def prepare_gs_data(camera_data: torch.Tensor, opt: LgmOptions = None) -> dict:
     poses = poses.clone()
     poses[:, :3, 1:3] *= -1
     view = torch.inverse(poses).transpose(1, 2)
-    return dict(input=rays.unsqueeze(0), cam_view=view.unsqueeze(0), cam_view_proj=(view @ proj).unsqueeze(0),
-                cam_pos=(-poses[:, :3, 3]).unsqueeze(0))
+    return view, view @ proj, -poses[:, :3, 3]
+
+
+def orbit_cameras(camera_data, num_views, elevation, camera_distance, opt: LgmOptions = None):
+    """Novel views of a generated set: ``num_views`` evenly spaced azimuths at ``elevation`` / ``camera_distance`` (the entrance's
+    orbit, camera.entrance_camera_data), expressed in the frame of the GENERATION set ``camera_data`` [1, T, 16] — prepare_gs_data
+    normalises a set to its own first camera, so the orbit reuses the generation set's transform instead of its own (else an orbit at
+    another elevation would show the asset tilted).  -> (cam_view, cam_view_proj) [1, num_views, 4, 4]."""
+    from .camera import entrance_camera_data
+    opt = opt or LgmOptions()
+    transform = _gs_transform(_gs_cams(camera_data))
+    cam = _gs_cams(entrance_camera_data(int(num_views), elevation=elevation, camera_distance=camera_distance))
+    view, view_proj, _ = _gs_view(transform.unsqueeze(0) @ cam, opt)
+    return view.unsqueeze(0), view_proj.unsqueeze(0)
 
 
 class LgmRefiner:
@@ -485,6 +513,20 @@ class LgmRefiner:
         z = autoencoder.encode_firsr_stage(small, scale_factor, parts=2, of=of)         # [2T, C, h, w]
         z = z.reshape(2, 1, T, z.shape[1], z.shape[2], z.shape[3]).permute(0, 1, 3, 2, 4, 5).contiguous()
         return z[0], z[1]
+
+    @torch.no_grad()
+    def gaussians_from_views(self, decoded_key_views, gs_data):
+        """The LGM once on a FINAL sample's key views (the 3-D export's starting point): ``decoded_key_views`` [4, 3, S, S] in [-1, 1]
+        (views [0, 6, 12, 18] of 24, else i * F // 4, as in ``latent_z``) with their rays from ``gs_data`` -> activated Gaussians
+        [1, N, 14] (a copy: the engine's output buffer is reused by the next refined step)."""
+        F_ = gs_data["input"].shape[1]
+        idxs = [0, 6, 12, 18] if F_ == 24 else [i * F_ // 4 for i in range(4)]
+        S = self.opt.input_size
+        if tuple(decoded_key_views.shape) != (4, 3, S, S):
+            raise ValueError(f"LGM expects 4 decoded {S}x{S} key views, got {tuple(decoded_key_views.shape)}")
+        rays = self._dev_const(gs_data, "rays", lambda: gs_data["input"][0, idxs].to(self.device, torch.float32).contiguous())
+        ops.lgm_pack_input(decoded_key_views.to(self.device, torch.float32).contiguous(), rays, self.inp)
+        return self.engine.forward_gaussians(self.inp).clone().unsqueeze(0)
 
     @torch.no_grad()
     def latent_z(self, eps_rows, ld, branch, xt, c_recip, c_recipm1, autoencoder, gs_data, scale_factor=0.18215, views=None,
