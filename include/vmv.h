@@ -44,7 +44,7 @@ int vmv_elem_type(void);
 int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
- * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams */
+ * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams, 107 = VmvGsSsimLossParams */
 int vmv_sizeof(int which);
 /* human-readable text for a code returned by any launcher (VMV_E* or hipError_t) */
 const char* vmv_error_string(int code);
@@ -523,6 +523,7 @@ int vmv_gs_batch_render(const VmvGsBatchParams* p, void* stream);
  *                                                  transmittance final_T and n_contrib = the number of the tile's instances, in blend
  *                                                  order, up to and including the last one the pixel blended (the early-stop point)
  *   vmv_gs_image_loss(image, target, ...)        MSE, its gradient dL_dimage and the loss (deterministic sum)
+ *     (or vmv_gs_ssim_loss(&l): the L1 + D-SSIM objective below, the same outputs)
  *   vmv_gs_batch_backward(&p)                    dL_dimage -> grad [B][N][14] in the activated layout of `gaussians`
  *   vmv_gs_adam_step(&adam)                      raw parameters, moments, activated [B * N][14] for the next iteration's pass
  * WORKSPACE LIFETIME: everything the pass wrote (preprocess arrays, scan_temp, keys / vals_sorted, ranges, out_color) and final_T /
@@ -565,6 +566,30 @@ typedef struct {
     float beta1, beta2, eps;
 } VmvGsAdamParams;
 int vmv_gs_adam_step(const VmvGsAdamParams* p, void* stream);
+
+/* L1 + D-SSIM, the objective of 3-D Gaussian Splatting (Kerbl et al. 2023), as an alternative to vmv_gs_image_loss (additive: ABI 11):
+ *   objective = (1 - lambda) mean|I - T| + lambda (1 - SSIM),  SSIM = the mean over all planes * height * width pixels of
+ *   m = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  C1 = 0.01^2, C2 = 0.03^2,
+ *   mu1 = g*I, mu2 = g*T, s11 = g*(I^2) - mu1^2, s22 = g*(T^2) - mu2^2, s12 = g*(I T) - mu1 mu2,  g* = the separable 11 x 11 Gaussian
+ *   window (sigma 1.5, taps normalised to sum 1) with ZERO padding of 5 (border pixels see zeros, the window is not renormalised).
+ * Every [height][width] plane is independent (a colour channel of a view); height or width below 11 is legal.
+ * dL_dimage = (1 - lambda) sign(I - T) / n - lambda dSSIM/dI with sign(0) = 0; NULL: the three scalars only (the metric path; the
+ * same bits as with a gradient).  loss: THREE floats on the device: objective, L1, mean SSIM.  Deterministic: per-block partial sums,
+ * then one block sums them in a fixed order; no atomics.  The workspace holds the three derivative maps of SSIM between the forward
+ * and the backward kernel, and the partials.  Argument checks run before any launch: VMV_ENULL, VMV_EINVAL (sizes <= 0, lambda outside [0, 1], workspace too
+ * small), VMV_ERANGE (planes * height * width >= 2^31). */
+typedef struct {
+    const float* image;          /* [planes][height][width] */
+    const float* target;         /* same shape */
+    int32_t planes, height, width;
+    float lambda_dssim;          /* in [0, 1]: 0 = pure L1, 1 = pure D-SSIM */
+    float* dL_dimage;            /* same shape, or NULL: scalars only */
+    float* loss;                 /* 3 floats on the device: objective, L1, mean SSIM */
+    float* workspace;            /* >= vmv_gs_ssim_loss_workspace_bytes(planes, height, width) */
+    size_t workspace_bytes;
+} VmvGsSsimLossParams;
+int vmv_gs_ssim_loss_workspace_bytes(int planes, int height, int width, size_t* bytes);
+int vmv_gs_ssim_loss(const VmvGsSsimLossParams* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Block permute-copy (frame-sharded sampling, DESIGN.md §8: packs / unpacks the all-to-all buffers that switch an

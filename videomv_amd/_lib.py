@@ -125,6 +125,12 @@ class GsAdamParams(C.Structure):
                 ("eps", C.c_float)]
 
 
+class GsSsimLossParams(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("target", C.c_void_p), ("planes", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("lambda_dssim", C.c_float), ("dL_dimage", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 class CopyParams(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("inner16", C.c_int32), ("ss0", C.c_int64), ("ss1", C.c_int64), ("ss2", C.c_int64)]
@@ -207,6 +213,8 @@ SYMBOLS = {
     "vmv_gs_batch_backward": (C.c_int, [C.POINTER(GsBackwardParams), _P]),
     "vmv_gs_image_loss": (C.c_int, [_P, _P, C.c_long, _P, _P, _P, _P]),
     "vmv_gs_adam_step": (C.c_int, [C.POINTER(GsAdamParams), _P]),
+    "vmv_gs_ssim_loss_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "vmv_gs_ssim_loss": (C.c_int, [C.POINTER(GsSsimLossParams), _P]),
     "vmv_latent_to_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_latent_to_rows_keep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_i2v_temporal_adapter": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
@@ -261,7 +269,7 @@ def load():
     if lib.vmv_elem_type() != (ELEM_F16 if _elem == "f16" else ELEM_BF16):
         raise RuntimeError(f"{LIB_PATH} was built for another element type")
     for which, st in ((OP_GEMM, GemmParams), (OP_GN_STATS, GroupNormParams), (OP_LAYERNORM, LayerNormParams),
-                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
+                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
         if lib.vmv_sizeof(which) != C.sizeof(st):
             raise RuntimeError(f"struct layout drift for {st.__name__}: C {lib.vmv_sizeof(which)} vs ctypes "
                                f"{C.sizeof(st)}")

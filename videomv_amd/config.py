@@ -68,6 +68,8 @@ def default_cfg() -> AttrDict:
     c.save_gaussians = False          # export a 3-D Gaussian asset for each sample
     c.gs_fit_iters = 0                # iterations fitting the LGM's Gaussians to the generated views (0: the feed-forward Gaussians)
     c.gs_fit_lr_scale = 1.0           # scales the fit's per-group learning rates (gs_fit.DEFAULT_LR)
+    c.gs_fit_loss = 'mse'             # the fit's objective: mse | l1_dssim = (1 - lambda) L1 + lambda (1 - SSIM) (csrc/gs_ssim.hip)
+    c.gs_fit_lambda_dssim = 0.2       # lambda of l1_dssim, in [0, 1] (3-D Gaussian Splatting: 0.2)
     c.gs_orbit_views = 0              # novel views rendered around the asset (0: none)
     c.gs_orbit_elevation = None       # their elevation (None: the entrance's)
     c.gs_orbit_size = None            # their image size (None: lgm_opt.output_size)

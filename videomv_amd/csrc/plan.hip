@@ -58,6 +58,7 @@ extern "C" int vmv_sizeof(int which) {
         case 104: return (int)sizeof(VmvGsBatchParams);
         case 105: return (int)sizeof(VmvGsBackwardParams);
         case 106: return (int)sizeof(VmvGsAdamParams);
+        case 107: return (int)sizeof(VmvGsSsimLossParams);
         default: return (int)op_size(which);
     }
 }

@@ -392,13 +392,24 @@ def worker_i2v(gpu, cfg, cfg_update):
 
 def _check_export_cfg(cfg, use_lgm):
     """`save_gaussians` (not a reference key) exports the LGM-refined loop's Gaussians: refuse it, before any sampling, where that loop
-    does not run or cannot run (the LGM renders square views only)."""
+    does not run or cannot run (the LGM renders square views only), or where the fit's objective is not one the fitter knows."""
     if not cfg.get('save_gaussians'):
         return
     if not use_lgm:
         raise ValueError("save_gaussians needs the LGM-refined loop: set UNet.use_lgm_refine True (and no cfg_parallel)")
     if int(cfg.resolution[0]) != int(cfg.resolution[1]):
         raise ValueError(f"save_gaussians: the LGM branch renders square views, resolution {list(cfg.resolution)} is not square")
+    from .gs_fit import check_loss
+    try:
+        check_loss(*_fit_loss(cfg))
+    except ValueError as e:
+        raise ValueError(f"save_gaussians: gs_fit_loss / gs_fit_lambda_dssim: {e}") from None
+
+
+def _fit_loss(cfg):
+    """-> (gs_fit_loss, gs_fit_lambda_dssim) with their defaults"""
+    lam = cfg.get('gs_fit_lambda_dssim')
+    return str(cfg.get('gs_fit_loss') or 'mse'), 0.2 if lam is None else float(lam)
 
 
 @torch.no_grad()
@@ -419,13 +430,17 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
     if rec['fit_iters'] > 0:
         from .gs_fit import GaussianFitter
         bg = (refiner.bg_color,) * 3
+        loss, lam = _fit_loss(cfg)
         fitter = GaussianFitter(g[0], gs_data['cam_view'][0], gs_data['cam_view_proj'][0], (views * 0.5 + 0.5).contiguous(), bg=bg,
-                                lr_scale=float(cfg.get('gs_fit_lr_scale') or 1.0), fovy=opt.fovy, znear=opt.znear, zfar=opt.zfar)
+                                lr_scale=float(cfg.get('gs_fit_lr_scale') or 1.0), fovy=opt.fovy, znear=opt.znear, zfar=opt.zfar,
+                                loss=loss, lambda_dssim=lam)
         st = fitter.fit(rec['fit_iters'])
         g = fitter.gaussians().unsqueeze(0)
         rec.update(st)
         logging.info(f"gs fit: {rec['fit_iters']} iterations on {F_} views, PSNR {st['psnr_before']:.2f} -> {st['psnr_after']:.2f} dB "
-                     f"(loss {st['loss_before']:.3e} -> {st['loss_after']:.3e}), {st['ms_per_iter']:.2f} ms/iteration, "
+                     f"(loss {st['loss_before']:.3e} -> {st['loss_after']:.3e})"
+                     + (f", SSIM {st['ssim_before']:.4f} -> {st['ssim_after']:.4f}" if 'ssim_after' in st else "")
+                     + f", {st['ms_per_iter']:.2f} ms/iteration, "
                      f"{st['instances']} instances")
     rec['vertices'] = refiner.renderer.save_ply(g, rec['ply'])
     logging.info(f"Save 3D Gaussians ({rec['vertices']} of {g.shape[1]}) to {rec['ply']}")

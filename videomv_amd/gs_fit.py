@@ -4,9 +4,12 @@
 The reference's last stage, reconstruction from the generated views, is unreleased (its README lists it as to-do); its LGM trains
 on an image MSE (``core/models.py:169``) and exports with ``save_ply`` (``core/gs.py:97``).  Here the LGM's feed-forward Gaussians
 of the final sample are the starting point and every generated view is a target.  One iteration on one stream: batched preprocess
--> ONE host read of the instance total -> forward with saved state -> MSE + dL/dimage -> blend backward -> preprocess backward and
+-> ONE host read of the instance total -> forward with saved state -> loss + dL/dimage -> blend backward -> preprocess backward and
 view sum -> fused Adam step on the raw parameters (logit opacity, log scale, raw quaternion, SH-DC colour: the .ply layout), which
 writes the activated Gaussians the next forward reads.  N stays fixed (no densification or pruning).
+
+The loss is the image MSE (``loss="mse"``, the default) or the objective of 3-D Gaussian Splatting, ``(1 - lambda) L1 + lambda
+(1 - SSIM)`` (``loss="l1_dssim"``, ``csrc/gs_ssim.hip``); ``ssim()`` is that kernel's forward as a metric.
 """
 import ctypes as C
 import math
@@ -32,16 +35,65 @@ def gaussians_to_raw(g):
                       (g[..., 11:14] - 0.5) / SH_C0], dim=-1)
 
 
+LOSSES = ("mse", "l1_dssim")
+
+
 def psnr(mse):
     return float("inf") if mse <= 0 else -10.0 * math.log10(mse)
 
 
+def check_loss(loss, lambda_dssim):
+    """ValueError for an unknown loss name or a D-SSIM weight outside [0, 1] (the fitter's and the entrances' common check)."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss {loss!r}: one of {LOSSES}")
+    if not 0.0 <= float(lambda_dssim) <= 1.0:
+        raise ValueError(f"lambda_dssim {lambda_dssim}: the D-SSIM weight lies in [0, 1]")
+
+
+def ssim_workspace(planes, height, width, device):
+    """the workspace of vmv_gs_ssim_loss for [planes, height, width] images, as a float tensor"""
+    nbytes = C.c_size_t(0)
+    L.check(L.load().vmv_gs_ssim_loss_workspace_bytes(planes, height, width, C.byref(nbytes)), "gs_ssim_loss_workspace_bytes")
+    return torch.empty((int(nbytes.value) + 3) // 4, dtype=torch.float32, device=device)
+
+
+def ssim_loss_params(image, target, lambda_dssim, dL, loss, workspace):
+    """the argument block of vmv_gs_ssim_loss for contiguous fp32 tensors [..., H, W] (dL: None for the scalars only)"""
+    p = L.GsSsimLossParams()
+    p.image, p.target = image.data_ptr(), target.data_ptr()
+    p.height, p.width = image.shape[-2], image.shape[-1]
+    p.planes = image.numel() // (p.height * p.width)
+    p.lambda_dssim = float(lambda_dssim)
+    p.dL_dimage = dL.data_ptr() if dL is not None else None
+    p.loss, p.workspace, p.workspace_bytes = loss.data_ptr(), workspace.data_ptr(), workspace.numel() * 4
+    return p
+
+
+def ssim(image, target):
+    """Mean SSIM (11 x 11 Gaussian window, sigma 1.5, zero padding: the 3-D GS / pytorch-ssim definition) of two GPU tensors
+    [..., H, W] of equal shape with values in [0, 1]; every [H, W] plane is independent.  The forward of csrc/gs_ssim.hip."""
+    if image.shape != target.shape or image.dim() < 2:
+        raise ValueError(f"ssim: shapes {tuple(image.shape)} and {tuple(target.shape)}")
+    if image.device.type != "cuda" or target.device != image.device:
+        raise RuntimeError("ssim runs on the HIP kernel: both images must be on the same GPU")
+    a, b = image.detach().to(torch.float32).contiguous(), target.detach().to(torch.float32).contiguous()
+    H, W = a.shape[-2], a.shape[-1]
+    with torch.cuda.device(a.device):
+        ws = ssim_workspace(a.numel() // (H * W), H, W, a.device)
+        out = torch.zeros(3, dtype=torch.float32, device=a.device)
+        L.check(L.load().vmv_gs_ssim_loss(C.byref(ssim_loss_params(a, b, 1.0, None, out, ws)), _stream_ptr()), "gs_ssim_loss")
+        return float(out[2].item())
+
+
 class GaussianFitter:
     """gaussians [N, 14] or [B, N, 14] (activated), cam_view / cam_view_proj [V, 4, 4] or [B, V, 4, 4], targets [V, 3, S, S] or
-    [B, V, 3, S, S] in [0, 1], bg: 3 floats.  ``lr``: dict overriding ``DEFAULT_LR``; ``lr_scale`` multiplies every group."""
+    [B, V, 3, S, S] in [0, 1], bg: 3 floats.  ``lr``: dict overriding ``DEFAULT_LR``; ``lr_scale`` multiplies every group.
+    ``loss``: "mse" or "l1_dssim" = (1 - lambda_dssim) L1 + lambda_dssim (1 - SSIM)."""
 
     def __init__(self, gaussians, cam_view, cam_view_proj, targets, bg=(0.5, 0.5, 0.5), lr=None, lr_scale=1.0, fovy=39.6,
-                 znear=0.5, zfar=2.5, betas=(0.9, 0.999), eps=1e-15):
+                 znear=0.5, zfar=2.5, betas=(0.9, 0.999), eps=1e-15, loss="mse", lambda_dssim=0.2):
+        check_loss(loss, lambda_dssim)
+        self.loss_name, self.lambda_dssim = loss, float(lambda_dssim)
         g = gaussians if gaussians.dim() == 3 else gaussians.unsqueeze(0)
         cv = cam_view if cam_view.dim() == 4 else cam_view.unsqueeze(0)
         cvp = cam_view_proj if cam_view_proj.dim() == 4 else cam_view_proj.unsqueeze(0)
@@ -82,6 +134,11 @@ class GaussianFitter:
         self.grad_view = torch.empty(VV * self.N, 14, dtype=torch.float32, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_ws = torch.empty(1024, dtype=torch.float32, device=dev)
+        self.mse = self.loss                           # where _mse() writes
+        if loss == "l1_dssim":                         # objective, L1, mean SSIM; the derivative maps and partials of csrc/gs_ssim.hip
+            self.loss3 = torch.zeros(3, dtype=torch.float32, device=dev)
+            self.loss, self.mse = self.loss3[:1], torch.zeros(1, dtype=torch.float32, device=dev)
+            self.ssim_ws = ssim_workspace(VV * 3, S, S, dev)
         self.num_rendered = 0
         self._adam(0)                                  # activated Gaussians of the raw parameters (what the first forward reads)
 
@@ -136,8 +193,17 @@ class GaussianFitter:
         return q
 
     def _loss(self, with_grad=True):
+        """The objective (-> ``loss``) and, ``with_grad``, dL/dimage of the last forward.  l1_dssim: ``loss`` is the first element of
+        ``loss3`` = objective, L1, mean SSIM."""
+        if self.loss_name == "l1_dssim":
+            p = ssim_loss_params(self.image, self.targets, self.lambda_dssim, self.dL if with_grad else None, self.loss3, self.ssim_ws)
+            L.check(L.load().vmv_gs_ssim_loss(C.byref(p), _stream_ptr()), "gs_ssim_loss")
+            return
+        self._mse(with_grad)
+
+    def _mse(self, with_grad):
         L.check(L.load().vmv_gs_image_loss(self.image.data_ptr(), self.targets.data_ptr(), self.image.numel(),
-                                           self.dL.data_ptr() if with_grad else None, self.loss.data_ptr(), self.loss_ws.data_ptr(),
+                                           self.dL.data_ptr() if with_grad else None, self.mse.data_ptr(), self.loss_ws.data_ptr(),
                                            _stream_ptr()), "gs_image_loss")
 
     def _backward(self, q):
@@ -161,21 +227,41 @@ class GaussianFitter:
     def evaluate(self):
         """-> MSE of the current Gaussians against the targets (forward + loss, no update)."""
         self._forward()
+        self._mse(False)
+        return float(self.mse.item())
+
+    def _evaluate_objective(self):
+        """l1_dssim: one forward -> (objective, mean SSIM, MSE) of the same renders."""
+        self._forward()
         self._loss(with_grad=False)
-        return float(self.loss.item())
+        objective, _, s = self.loss3.tolist()
+        self._mse(False)
+        return objective, s, float(self.mse.item())
 
     def fit(self, iters):
-        """``iters`` iterations -> dict(loss_before, loss_after, psnr_before, psnr_after, ms_per_iter, iters, instances)."""
-        before = self.evaluate()
+        """``iters`` iterations -> dict(loss_before, loss_after, psnr_before, psnr_after, ms_per_iter, iters, instances).  ``loss_*`` is
+        the optimised objective.  With l1_dssim also mse_before / mse_after (what psnr_* is computed from) and ssim_before /
+        ssim_after, the objective's own third scalar."""
+        dssim = self.loss_name == "l1_dssim"
+        if dssim:
+            before, ssim_before, mse_before = self._evaluate_objective()
+        else:
+            before = mse_before = self.evaluate()
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         for _ in range(int(iters)):
             self.step()
         torch.cuda.synchronize(self.device)
         ms = (time.perf_counter() - t0) * 1e3 / max(1, int(iters))
-        after = self.evaluate()
-        return dict(loss_before=before, loss_after=after, psnr_before=psnr(before), psnr_after=psnr(after), ms_per_iter=ms,
-                    iters=int(iters), instances=self.num_rendered)
+        if dssim:
+            after, ssim_after, mse_after = self._evaluate_objective()
+        else:
+            after = mse_after = self.evaluate()
+        st = dict(loss_before=before, loss_after=after, psnr_before=psnr(mse_before), psnr_after=psnr(mse_after), ms_per_iter=ms,
+                  iters=int(iters), instances=self.num_rendered)
+        if dssim:
+            st.update(mse_before=mse_before, mse_after=mse_after, ssim_before=ssim_before, ssim_after=ssim_after)
+        return st
 
     def gaussians(self):
         """activated Gaussians [N, 14] (or [B, N, 14] for B > 1), a copy"""
