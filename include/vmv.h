@@ -217,6 +217,11 @@ int vmv_gemm_pick_tile(const VmvGemmParams* p);
  * would return otherwise.  Needs no GPU.  The Python host calls it when a measured (tile, split-K) entry of tuned_gemm.json is about
  * to be forced on a recorded launch: a stale entry is dropped there, with a warning, instead of aborting the first replay. */
 int vmv_gemm_validate(const VmvGemmParams* p);
+/* The block -> tile map every GEMM kernel uses (XCD-aware bijection, grouped order for gm > 1), on the host: the (row tile, column
+ * tile) block `bid` of a tiles_m x tiles_n grid works on.  VMV_EINVAL unless 0 <= bid < tiles_m * tiles_n and gm >= 1.  Needs no GPU. */
+int vmv_gemm_tile_map(int bid, int tiles_m, int tiles_n, int gm, int* tile_m, int* tile_n);
+/* the gm the launchers of the grouped kernels choose for a grid of BM x BN tiles with `conc` blocks running at once per XCD */
+int vmv_gemm_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc);
 
 /* ------------------------------------------------------------------------------------------------------
  * FeedForward of a BasicTransformerBlock in one launch (util.py:536-540 `x = ff(norm3(x)) + x`, FeedForward :553-578,

@@ -273,3 +273,66 @@ def test_gemm_validate_is_the_launch_without_the_device():
         assert len([x for x in w if "stale" in str(x.message)]) == 1
     finally:
         ops._TUNED, ops._STALE_WARNED = old, old_w
+
+
+def _tile_map_py(bid, tiles_m, tiles_n, gm):
+    """The kernels' block -> tile map (gemm_common.h), written out."""
+    nblk = tiles_m * tiles_n
+    q, r = nblk >> 3, nblk & 7
+    xcd, idx = bid & 7, bid >> 3
+    logical = (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + idx
+    if gm > 1:
+        gsz = gm * tiles_n
+        g = logical // gsz
+        first = g * gm
+        gmh = min(tiles_m - first, gm)          # the last group is clipped (gm > tiles_m included)
+        rem = logical - g * gsz
+        tn = rem // gmh
+        return first + (rem - tn * gmh), tn
+    return logical // tiles_n, logical % tiles_n
+
+
+def _group_m_py(tiles_m, tiles_n, BM, BN, conc):
+    if tiles_n < 2 or tiles_m < 2:
+        return 1
+    best, best_cost = 1, BM + conc * BN
+    gm = 2
+    while gm <= conc:
+        gn = (conc + gm - 1) // gm
+        if gn <= tiles_n and gm <= tiles_m and gm * BM + gn * BN < best_cost:
+            best, best_cost = gm, gm * BM + gn * BN
+        gm *= 2
+    return best
+
+
+def test_gemm_tile_map_is_a_bijection():
+    """Every block of a tiles_m x tiles_n grid gets its own tile, for the plain (gm = 1) and every grouped order, and the library's
+    map is the formula above (seven kernels share it)."""
+    lib = L.load()
+    tm, tn = C.c_int(), C.c_int()
+    cases = 0
+    for tiles_m in range(1, 41):
+        for tiles_n in range(1, 14):
+            for gm in (1, 2, 4, 8, 16, 32):
+                seen = set()
+                for bid in range(tiles_m * tiles_n):
+                    assert lib.vmv_gemm_tile_map(bid, tiles_m, tiles_n, gm, C.byref(tm), C.byref(tn)) == 0
+                    assert (tm.value, tn.value) == _tile_map_py(bid, tiles_m, tiles_n, gm), (bid, tiles_m, tiles_n, gm)
+                    assert 0 <= tm.value < tiles_m and 0 <= tn.value < tiles_n, (bid, tiles_m, tiles_n, gm)
+                    seen.add((tm.value, tn.value))
+                assert len(seen) == tiles_m * tiles_n, (tiles_m, tiles_n, gm)
+                cases += 1
+    assert cases == 3120
+    assert lib.vmv_gemm_tile_map(6, 2, 3, 1, C.byref(tm), C.byref(tn)) == -1
+    assert lib.vmv_gemm_tile_map(0, 2, 3, 0, C.byref(tm), C.byref(tn)) == -1
+    assert lib.vmv_gemm_tile_map(0, 2, 3, 1, None, C.byref(tn)) == -3
+
+
+def test_gemm_group_m_matches_its_formula():
+    lib = L.load()
+    for conc in (32, 64):
+        for BM, BN in ((256, 320), (256, 128), (128, 160), (512, 128)):
+            for tiles_m in range(1, 41):
+                for tiles_n in range(1, 14):
+                    assert lib.vmv_gemm_group_m(tiles_m, tiles_n, BM, BN, conc) == _group_m_py(tiles_m, tiles_n, BM, BN, conc), \
+                        (tiles_m, tiles_n, BM, BN, conc)

@@ -238,6 +238,55 @@ def test_gemm_splitk_wide_tile(tile, M, N, K, ks):
     check(dev["out"], cpu["a"].float() @ cpu["w"].float().t() + cpu["b"] + cpu["res"].float())
 
 
+_RUNWISE_CASES = {}
+
+
+def _runwise_case(kind):
+    """Operands and the torch reference of the two run-wise split-K cases, built once for the three tiles."""
+    if kind not in _RUNWISE_CASES:
+        Cc = N = 128
+        if kind == "spatial":               # one 128 x 128 image, 3 x 3 taps: 18 chunks of 64, four splits of 5 / 5 / 5 / 3
+            hh = ww = 128
+            M, ks = hh * ww, 4
+            wt = torch.randn(N, Cc, 3, 3, generator=g(2)) * (9 * Cc) ** -0.5
+            w = P.pack_conv3x3(wt, "cpu")
+        else:                               # B = 2, F = 24, P = 352, three temporal taps: 6 chunks, three splits of 2
+            Bn, F_, Pp = 2, 24, 352
+            M, ks = Bn * F_ * Pp, 3
+            wt = torch.randn(N, Cc, 3, 1, 1, generator=g(2)) * (3 * Cc) ** -0.5
+            w = P.pack_tconv(wt, "cpu")
+        t = dict(x=rnd((M, Cc), 1), w=w, b=torch.randn(N, generator=g(3)), res=rnd((M, N), 5))
+        if kind == "spatial":
+            x4 = t["x"].float().view(1, hh, ww, Cc).permute(0, 3, 1, 2)
+            ref = torch.nn.functional.conv2d(x4, wt.to(BF).float(), t["b"], padding=1).permute(0, 2, 3, 1).reshape(M, N)
+        else:
+            x5 = t["x"].float().view(Bn, F_, Pp, Cc).permute(0, 3, 1, 2)[..., None]
+            ref = torch.nn.functional.conv3d(x5, wt.to(BF).float(), t["b"], padding=(1, 0, 0))[..., 0].permute(0, 2, 3, 1).reshape(M, N)
+        _RUNWISE_CASES[kind] = (M, N, Cc, ks, t, ref + t["res"].float())
+    return _RUNWISE_CASES[kind]
+
+
+@pytest.mark.parametrize("tile", [L.TILE_256x128, L.TILE_G128x128, L.TILE_PP256x128])
+@pytest.mark.parametrize("kind", ["spatial", "temporal"])
+def test_gemm_splitk_conv_runwise(kind, tile):
+    """Split-K on gemm_glds.hip with the run-wise K walk on (a convolution over M >= 16384 rows): the walk is chunk-major over the taps
+    of a run, split-K counts chunks in walk order, so the splits start in the MIDDLE of a run — at (chunk, tap) = (0, 5), (1, 1), (1, 6)
+    of the 3 x 3 case and (0, 2), (1, 1) of the temporal one — and the fast-forward has to land on the right tap, channel chunk and W
+    column.  Bias and residual go through the shared reduce pass."""
+    M, N, Cc, ks, t, ref = _runwise_case(kind)
+    c = Case(out=torch.zeros(M, N, dtype=BF), ws=torch.zeros(ks * M * N), **t)
+
+    def build(d):
+        if kind == "spatial":
+            segs, geom = ops.conv3x3_segs([(d["x"], Cc, Cc)]), ops.Geom(OH=128, OW=128, IH=128, IW=128)
+        else:
+            segs, geom = ops.temporal_segs(d["x"], Cc, Cc), ops.Geom(F=24, P=352)
+        return ops.gemm_params(M, N, segs, d["w"], d["out"], N, bias=d["b"], residual=d["res"], ldr=N, geom=geom,
+                               ksplit=ks, workspace=d["ws"], tile=tile)
+    cpu, dev = run_gemm(build, c, cpu_ref=False)
+    check(dev["out"], ref)
+
+
 @pytest.mark.parametrize("n,H,W,Cin,N,fp32,ldo", [(2, 20, 37, 128, 4, True, 4), (3, 9, 16, 320, 4, False, 8), (2, 8, 8, 512, 8, True, 8),
                                                    (1, 33, 50, 192, 4, True, 4), (2, 16, 17, 160, 4, True, 4), (1, 5, 3, 32, 8, False, 8),
                                                    (24, 40, 64, 320, 4, True, 4)])

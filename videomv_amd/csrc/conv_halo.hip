@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const VmvGemmParams p, c
             const int s = sp ^ ((P >> pshift) & (SL - 1));
             const bool ok = P < CH_HPX && y >= 0 && y < H && x >= 0 && x < W;
             const uint32_t vo = ok ? (uint32_t)((y * W + x) * ld + c0 + s * 8) * 2u : OOB;
-            VMV_BLDS16(a_rsrc, halo + q0 * 16, vo, 0);
+            blds16(a_rsrc, halo + q0 * 16, vo, 0);
         }
         // ---- weights of the chunk: piece ((tap * KS + ks) * Nr + m) * 4 + kg  <-  W[m][tap * C + c0 + ks * 32 + kg * 8 .. + 8]
         const int nwp = 9 * KS * Nr * 4;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(const VmvGemmParams p, c
             const int kg = q & 3, m = (q >> 2) % Nr, rest = (q >> 2) / Nr;
             const int ks = rest % KS, tap = rest / KS;
             const uint32_t vo = q < nwp ? (uint32_t)(m * p.ktot + tap * C + c0 + ks * 32 + kg * 8) * 2u : OOB;
-            VMV_BLDS16(w_rsrc, wlds + q0 * 16, vo, 0);
+            blds16(w_rsrc, wlds + q0 * 16, vo, 0);
         }
         wait_vmcnt<0>();
         __syncthreads();
@@ -155,7 +155,7 @@ bool vmv_conv_halo_supported(const VmvGemmParams& p) {
         if (s.d0 != t / 3 - 1 || s.d1 != t % 3 - 1) return false;
     }
     if ((p.seg[0].ld & 7) || !vmv_aligned16(p.seg[0].src) || !vmv_aligned16(p.W)) return false;
-    if ((long)p.OH * p.OW * p.seg[0].ld * 2 >= (1L << 31) - 65536) return false;
+    if (!vmv_span32((long)p.OH * p.OW, p.seg[0].ld)) return false;
     if (p.out_fp32 ? (((uintptr_t)p.out) & 3) != 0 : (((uintptr_t)p.out) & 1) != 0) return false;
     if (p.ldo < p.N) return false;
     return true;

@@ -59,17 +59,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(const VmvGemmParams p, const 
     const int wave = tid >> 6;
     const int wave_m = wave >> 1, wave_n = wave & 1;
 
-    // ---- XCD-aware tile mapping (bijective for any block count)
-    const int nblk = tiles_m * tiles_n;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int tile_n = logical % tiles_n;
-    const int tile_m = logical / tiles_n;
+    // ---- XCD-aware tile mapping (gemm_common.h)
+    int tile_m, tile_n;
+    tile_of_block(blockIdx.x, tiles_m, tiles_n, 1, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int split = blockIdx.y;
     const int step_begin = split * steps_per_split;
@@ -441,6 +433,15 @@ extern "C" int vmv_gemm_validate(const VmvGemmParams* pp) {
     return rc;
 }
 
+// the kernels' block -> tile map and the launchers' group size, for the host-side tests (gemm_common.h)
+extern "C" int vmv_gemm_tile_map(int bid, int tiles_m, int tiles_n, int gm, int* tile_m, int* tile_n) {
+    if (!tile_m || !tile_n) return VMV_ENULL;
+    if (tiles_m <= 0 || tiles_n <= 0 || gm < 1 || bid < 0 || (long)bid >= (long)tiles_m * tiles_n) return VMV_EINVAL;
+    tile_of_block(bid, tiles_m, tiles_n, gm, *tile_m, *tile_n);
+    return VMV_OK;
+}
+extern "C" int vmv_gemm_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc) { return gemm_group_m(tiles_m, tiles_n, BM, BN, conc); }
+
 extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
     if (!pp) return VMV_ENULL;
     const VmvGemmParams& p = *pp;
@@ -481,7 +482,7 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
                                    // addressed with 32-bit byte offsets from W
         if (p.wgroup_rows < 0 || (p.wgroup_rows & 255) || p.wgroup_stride < 0 || (p.wgroup_stride & 7) || p.ksplit > 1) return VMV_EINVAL;
         const long groups = ((long)p.M + p.wgroup_rows - 1) / p.wgroup_rows;
-        if (((groups - 1) * p.wgroup_stride + (long)p.N * p.ktot) * 2 >= (1L << 31) - 65536) return VMV_ERANGE;
+        if (!vmv_span32(1, (groups - 1) * p.wgroup_stride + (long)p.N * p.ktot)) return VMV_ERANGE;
     }
     if (p.gn_table && !vmv_gemm_rs_supported(p) && !vmv_gemm_tfr_supported(p)) return VMV_EINVAL;      // folded GroupNorm: gemm_rs / gemm_tfr only
     if (p.gn_silu && !(p.gn_table && vmv_gemm_tfr_supported(p))) return VMV_EINVAL;

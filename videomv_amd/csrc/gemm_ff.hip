@@ -78,8 +78,8 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         const __amdgpu_buffer_rsrc_t b1_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b1), 0, p.b1 ? 8u * FF_C * 4u : 0u, SRD_FLAGS);
         const __amdgpu_buffer_rsrc_t b2_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.b2), 0, p.b2 ? FF_C * 4u : 0u, SRD_FLAGS);
         for (int q = wave; q * 256 < 8 * FF_C; q += 8)
-            VMV_BLDS16(b1_rsrc, reinterpret_cast<unsigned char*>(b1_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
-        if (wave < 2) VMV_BLDS16(b2_rsrc, reinterpret_cast<unsigned char*>(b2_lds) + wave * 1024, (uint32_t)(wave * 256 + 4 * lane) * 4u, 0);
+            blds16(b1_rsrc, reinterpret_cast<unsigned char*>(b1_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
+        if (wave < 2) blds16(b2_rsrc, reinterpret_cast<unsigned char*>(b2_lds) + wave * 1024, (uint32_t)(wave * 256 + 4 * lane) * 4u, 0);
     }
     const __amdgpu_buffer_rsrc_t w1_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, 8u * FF_C * FF_C * 2u, SRD_FLAGS);
     const __amdgpu_buffer_rsrc_t w2_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2), 0, (uint32_t)FF_C * 4u * FF_C * 2u, SRD_FLAGS);
@@ -95,13 +95,13 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
             for (int q = 0; q < 5; ++q) {
                 const int u = wave * 320 + q * 64 + ln;
                 const int r = u / 40, s = u - r * 40;
-                VMV_BLDS16(w1_rsrc, base + wave * 5120 + q * 1024, (uint32_t)(r * FF_C + (s ^ ((r >> 1) & 7)) * 8) * 2u, so);
+                blds16(w1_rsrc, base + wave * 5120 + q * 1024, (uint32_t)(r * FF_C + (s ^ ((r >> 1) & 7)) * 8) * 2u, so);
             }
         }
         {   // W2: 20 pieces, wave w takes w, w + 8, w + 16
             const uint32_t so = (uint32_t)(c * FF_HC) * 2u;
             for (int t = wave; t < 20; t += 8)
-                VMV_BLDS16(w2_rsrc, base + FF_W1_BYTES + t * 1024, (uint32_t)((16 * t + (lane >> 2)) * (4 * FF_C) + w2_slot * 8) * 2u, so);
+                blds16(w2_rsrc, base + FF_W1_BYTES + t * 1024, (uint32_t)((16 * t + (lane >> 2)) * (4 * FF_C) + w2_slot * 8) * 2u, so);
         }
     };
     issue_chunk(0, 0);
@@ -247,8 +247,8 @@ extern "C" int vmv_ff_fused_ok(const VmvFfParams* pp) {
     if ((p.ldx & 7) || (p.ldo & 7) || (p.residual && (p.ldr & 7))) return 0;
     if (!vmv_aligned16(p.x) || !vmv_aligned16(p.w1) || !vmv_aligned16(p.w2) || !vmv_aligned16(p.out) || (p.residual && !vmv_aligned16(p.residual))) return 0;
     if ((p.b1 && !vmv_aligned16(p.b1)) || (p.b2 && !vmv_aligned16(p.b2))) return 0;
-    if ((long)(p.M + 128) * p.ldx * 2 >= (1L << 31) - 65536 || (long)(p.M + 128) * p.ldo * 2 >= (1L << 31) - 65536) return 0;
-    if (p.residual && (long)(p.M + 128) * p.ldr * 2 >= (1L << 31) - 65536) return 0;
+    if (!vmv_span32(p.M + 128, p.ldx) || !vmv_span32(p.M + 128, p.ldo)) return 0;
+    if (p.residual && !vmv_span32(p.M + 128, p.ldr)) return 0;
     return 1;
 }
 

@@ -36,26 +36,9 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave >> 1, wave_n = wave & 1;
 
-    // ---- XCD-aware tile mapping (bijective)
-    const int nblk = tiles_m * tiles_n;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    // grouped order (round 6; gemm_xglds.hip): gm row tiles x 32 / gm column tiles run together on an XCD, so its L2 serves each W
-    // slice to gm row tiles instead of one (gm = 1: the N tiles of one row tile adjacent, as before)
+    // ---- XCD-aware tile mapping, grouped order (gemm_common.h)
     int tile_m, tile_n;
-    if (gm > 1) {
-        const int gsz = gm * tiles_n, g = logical / gsz, first = g * gm;
-        const int gmh = tiles_m - first < gm ? tiles_m - first : gm;
-        const int rem = logical - g * gsz;
-        tile_n = rem / gmh; tile_m = first + (rem - tile_n * gmh);
-    } else {
-        tile_n = logical % tiles_n; tile_m = logical / tiles_n;
-    }
+    tile_of_block(blockIdx.x, tiles_m, tiles_n, gm, tile_m, tile_n);
     const int m0 = tile_m * GL_BM, n0 = tile_n * BN;
     const int split = blockIdx.y;
     const int step_begin = split * steps_per_split;
@@ -201,9 +184,9 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
         unsigned char* abase = smem + stage * Cfg::STAGE_BYTES + wave * 1024;
         unsigned char* wbase = smem + stage * Cfg::STAGE_BYTES + Cfg::A_BYTES;
 #pragma unroll
-        for (int i = 0; i < Cfg::NAI; ++i) VMV_BLDS16(c.a_rsrc, abase + i * (NW * 1024), a_off(c, i), c.a_so);
+        for (int i = 0; i < Cfg::NAI; ++i) blds16(c.a_rsrc, abase + i * (NW * 1024), a_off(c, i), c.a_so);
 #pragma unroll
-        for (int j = 0; j < Cfg::NWI; ++j) VMV_BLDS16(w_rsrc, wbase + wgrp[j] * 1024, c.kvalid ? wvo[j] : OOB, c.w_so);
+        for (int j = 0; j < Cfg::NWI; ++j) blds16(w_rsrc, wbase + wgrp[j] * 1024, c.kvalid ? wvo[j] : OOB, c.w_so);
         advance(c.segk);
     };
 
@@ -224,22 +207,9 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
     // multiply" phases of a plain loop leave the matrix pipe idle during the LDS burst), and the barrier of chunk t+1
     // sits between two MFMA batches that need no LDS.
     auto read_frags = [&](int slot_idx, int kk, elem8_t (&af)[WM], elem8_t (&wf)[WN]) {
-        const u32x4_t* a = reinterpret_cast<const u32x4_t*>(smem + slot_idx * Cfg::STAGE_BYTES) + (wave_m * 64 + frow) * 8;
-        const u32x4_t* w = reinterpret_cast<const u32x4_t*>(smem + slot_idx * Cfg::STAGE_BYTES + Cfg::A_BYTES) +
-                           (wave_n * 16 * WN + frow) * 8;
-        const int slot = (kk * 4 + fgrp) ^ fswz;
-#pragma unroll
-        for (int i = 0; i < WM; ++i) af[i] = __builtin_bit_cast(elem8_t, a[i * 16 * 8 + slot]);
-#pragma unroll
-        for (int j = 0; j < WN; ++j) wf[j] = __builtin_bit_cast(elem8_t, w[j * 16 * 8 + slot]);
+        vmvg::read_frags<Cfg>(smem, slot_idx, kk, wave_m, wave_n, frow, fgrp, fswz, af, wf);
     };
-    auto mma = [&](const elem8_t (&af)[WM], const elem8_t (&wf)[WN]) {
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-                acc[j][i] = VMV_MFMA16(wf[j], af[i], acc[j][i], 0, 0, 0);
-    };
+    auto mma = [&](const elem8_t (&af)[WM], const elem8_t (&wf)[WN]) { mma_tile(acc, af, wf); };
 
     elem8_t a0[WM], w0[WN], a1[WM], w1[WN];
     if constexpr (PP) {
@@ -285,8 +255,8 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
 #pragma unroll
                     for (int k = 0; k < Cfg::LPT; ++k) {
                         if (more) {
-                            if (k < Cfg::NAI) VMV_BLDS16(c.a_rsrc, abase + k * (NW * 1024), a_off(c, k < Cfg::NAI ? k : 0), c.a_so);
-                            else VMV_BLDS16(w_rsrc, wbase + wgrp[k - Cfg::NAI] * 1024, c.kvalid ? wvo[k - Cfg::NAI] : OOB, c.w_so);
+                            if (k < Cfg::NAI) blds16(c.a_rsrc, abase + k * (NW * 1024), a_off(c, k < Cfg::NAI ? k : 0), c.a_so);
+                            else blds16(w_rsrc, wbase + wgrp[k - Cfg::NAI] * 1024, c.kvalid ? wvo[k - Cfg::NAI] : OOB, c.w_so);
                         }
                         const int upto = (NRD * (k + 1)) / Cfg::LPT;
 #pragma unroll
@@ -434,9 +404,7 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
         uint16_t* outp = reinterpret_cast<uint16_t*>(p.out);
         const uint16_t* resp = reinterpret_cast<const uint16_t*>(p.residual);
         const float rs = p.res_scale != 0.f ? p.res_scale : 1.f;
-        // Store-data discipline (see gemm_pglds.hip): the stored registers are a VALU-written copy, never the destination
-        // of an LDS read, and the previous iteration's copy stays alive until this iteration's LDS read has returned — an
-        // LDS read returning into a pending store's data registers corrupts the store when the store path is backed up.
+        // store-data discipline (gemm_glds_common.h)
         u32x4_t sd_prev = u32x4_t{0u, 0u, 0u, 0u};
         for (int idx = tid; idx < GL_BM * U; idx += Cfg::NT) {
             const int r = idx / U, u = idx - r * U;
@@ -452,11 +420,8 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
                 v = pack8(a);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
-            asm volatile("" ::"v"(sd_prev));
-            u32x4_t sd;
-            asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
-                         : "=&v"(sd.x), "=&v"(sd.y), "=&v"(sd.z), "=&v"(sd.w)
-                         : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+            keep_alive(sd_prev);
+            const u32x4_t sd = valu_copy(v);
             *reinterpret_cast<u32x4_t*>(outp + (size_t)m * p.ldo + n) = sd;
             sd_prev = sd;
         }
@@ -472,31 +437,16 @@ __global__ __launch_bounds__(128 * WMW, WMW == 2 ? 2 : 1) void gemm_glds_kernel(
 // first level 570 -> 672 / 503 -> 585 TFLOP/s, 48-view encode 22.4 -> 20.6 ms, decode 7.7 -> 7.4 (profiles/r6_lgm_step_bench*.log).
 int glds_tapmajor(const VmvGemmParams& p) { return p.M >= 16384 ? 1 : 0; }
 
-// rows of the tile group that shares W slices in an XCD's L2 (gemm_xglds.hip xglds_group_m; `conc` = blocks an XCD runs at once:
-// 32 CUs x 1 or 2 blocks).
-int glds_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc) {
-    if (tiles_n < 2 || tiles_m < 2) return 1;
-    int best = 1, best_cost = BM + conc * BN;
-    for (int gm = 2; gm <= conc; gm *= 2) {
-        const int gn = (conc + gm - 1) / gm;
-        if (gn > tiles_n || gm > tiles_m) continue;
-        const int cost = gm * BM + gn * BN;
-        if (cost < best_cost) { best = gm; best_cost = cost; }
-    }
-    return best;
-}
-
 template <int WMW, int WN, int STAGES, bool PP = false>
 int launch_glds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     using Cfg = GlCfg<WMW, WN, STAGES>;
-    static_assert(Cfg::LPT >= 6 && Cfg::LPT <= 9 && (STAGES == 2 || 2 * Cfg::LPT <= 14), "wait_vmcnt literals");
     static_assert(Cfg::BM * (Cfg::BN * 2 + 16) <= Cfg::LDS_BYTES, "epilogue staging fits in the ring");
     const int tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
     const int tiles_n = (p.N + Cfg::BN - 1) / Cfg::BN;
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     const int sps = (total_steps + ks - 1) / ks;
     dim3 grid(tiles_m * tiles_n, ks, 1);
-    const int gm = glds_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, WMW == 2 ? 64 : 32);
+    const int gm = gemm_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, WMW == 2 ? 64 : 32);
     static std::atomic<unsigned long long> attr_set{0};
     if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_glds_kernel<WMW, WN, STAGES, PP>), Cfg::LDS_BYTES)) return rc_attr;
     VMV_LAUNCH((gemm_glds_kernel<WMW, WN, STAGES, PP>), grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, total_steps, sps, gm,
@@ -509,12 +459,8 @@ int launch_glds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
 // Called by vmv_gemm (gemm.hip) after argument validation.  The split-K reduce pass stays in gemm.hip.
 int vmv_gemm_glds_launch(const VmvGemmParams& p, int total_steps, int tile, hipStream_t st) {
     if (p.rowstat) return VMV_GLDS_UNSUPPORTED;          // LayerNorm-folded GEMMs: gemm_pglds.hip / gemm.hip epilogues only
-    // 32-bit byte offsets through buffer descriptors: every operand must span < 2 GiB
-    long maxrows = p.M;
-    if (p.OH > 0) { const long src_rows = (long)(p.M / (p.OH * p.OW) + 1) * p.IH * p.IW; if (src_rows > maxrows) maxrows = src_rows; }
-    for (int i = 0; i < p.nseg; ++i)
-        if (maxrows * (long)p.seg[i].ld * 2 >= (1L << 31) - 65536) return VMV_GLDS_UNSUPPORTED;
-    if ((long)p.N * p.ktot * 2 >= (1L << 31) - 65536) return VMV_GLDS_UNSUPPORTED;
+    // 32-bit byte offsets through buffer descriptors: every segment's source and W
+    if (!vmv_gemm_spans32(p, vmv_gemm_src_rows(p), 0, 0, 0)) return VMV_GLDS_UNSUPPORTED;
     if (tile == VMV_TILE_PP256x128) return launch_glds<4, 4, 3, true>(p, total_steps, st);
     if (tile == VMV_TILE_PP256x160) {
         if (p.epilogue == VMV_EPI_GEGLU) return VMV_EINVAL;

@@ -26,24 +26,14 @@ namespace {
 // NWM x 2 waves (NWM = 4: one block per CU, 3-stage ring; NWM = 2: two blocks per CU, 2-stage ring), wave tile
 // 16*WM x 16*WN, block tile 16*WM*NWM x 32*WN
 template <int NWM, int WM_, int WN>
-struct PgCfg {
-    static constexpr int NW = 2 * NWM, NT = 64 * NW;
-    static constexpr int STAGES = NWM == 4 ? 3 : 2;
-    static constexpr int BM = 16 * WM_ * NWM;
-    static constexpr int BN = 32 * WN;
-    static constexpr int A_BYTES = BM * 128;
-    static constexpr int W_BYTES = BN * 128;
-    static constexpr int STAGE_BYTES = A_BYTES + W_BYTES;
-    static constexpr int LDS_BYTES = STAGES * STAGE_BYTES;
-    static constexpr int NAI = BM / (8 * NW);              // A wave-instructions per wave per chunk (8 rows each)
-    static constexpr int NWI = (BN / 8 + NW - 1) / NW;
-    static constexpr int LPT = NAI + NWI;
+struct PgCfg : TileRingCfg<NWM, WM_, WN, (NWM == 4 ? 3 : 2)> {
+    using Ring = TileRingCfg<NWM, WM_, WN, (NWM == 4 ? 3 : 2)>;
+    using Ring::NW; using Ring::LDS_BYTES;
     static constexpr int STRIP = 640;                      // per wave: 16*WN bias values + 16*WN column sums (folded LayerNorm)
     static constexpr int STRIPS = STRIP * NW;              // per-wave strips behind the ring
     static constexpr int LDS_LIMIT = (NWM == 4 ? 160 : 80) * 1024;
     static constexpr bool DEDICATED = LDS_BYTES + STRIPS + NW * 2816 <= LDS_LIMIT;     // slabs behind the strips
     static constexpr int LDS_TOTAL = LDS_BYTES + STRIPS + (DEDICATED ? NW * 2816 : 0);
-    static_assert(BM % (8 * NW) == 0, "A rows split evenly over the waves");
 };
 
 // LNS: the (mean, rstd) of a LayerNorm folded into this GEMM (vmv.h, VmvGemmParams.ln_eps) are accumulated from the A
@@ -67,11 +57,8 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
     const int G = gridDim.x;
     const int bid = blockIdx.x;
 
-    auto item_tile = [&](int v, int& m0, int& n0) {      // XCD-aware bijection item -> tile (see gemm_glds.hip)
-        const int q = nitems >> 3, r = nitems & 7;
-        const int xcd = v & 7;
-        const int idx = v >> 3;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    auto item_tile = [&](int v, int& m0, int& n0) {      // XCD-aware bijection item -> tile (gemm_common.h): the N tiles of a row tile adjacent
+        const int logical = xcd_logical(v, nitems);
         const int tn = logical % tiles_n;
         m0 = (logical / tiles_n) * BM;
         n0 = tn * BN;
@@ -139,8 +126,8 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         return c;
     };
     auto issue_piece = [&](const ChunkCtx& c, const int q) {      // q: compile-time after unrolling
-        if (q < Cfg::NAI) VMV_BLDS16(c.a_rsrc, c.abase + q * (NW * 1024), c.kall ? avo[q < Cfg::NAI ? q : 0] : OOB, c.a_so);
-        else VMV_BLDS16(w_rsrc, c.wbase + wgrp[q >= Cfg::NAI ? q - Cfg::NAI : 0] * 1024,
+        if (q < Cfg::NAI) blds16(c.a_rsrc, c.abase + q * (NW * 1024), c.kall ? avo[q < Cfg::NAI ? q : 0] : OOB, c.a_so);
+        else blds16(w_rsrc, c.wbase + wgrp[q >= Cfg::NAI ? q - Cfg::NAI : 0] * 1024,
                         c.kall ? wvo[q >= Cfg::NAI ? q - Cfg::NAI : 0] : OOB, c.w_so);
     };
     auto advance_chunk = [&]() {
@@ -182,14 +169,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
     const int fgrp = lane >> 4;
     const int fswz = (frow >> 1) & 7;
     auto read_frags = [&](int slot_idx, int kk, elem8_t (&af)[WM], elem8_t (&wf)[WN]) {
-        const u32x4_t* a = reinterpret_cast<const u32x4_t*>(smem + slot_idx * Cfg::STAGE_BYTES) + (wave_m * 16 * WM + frow) * 8;
-        const u32x4_t* w = reinterpret_cast<const u32x4_t*>(smem + slot_idx * Cfg::STAGE_BYTES + Cfg::A_BYTES) +
-                           (wave_n * 16 * WN + frow) * 8;
-        const int slot = (kk * 4 + fgrp) ^ fswz;
-#pragma unroll
-        for (int i = 0; i < WM; ++i) af[i] = __builtin_bit_cast(elem8_t, a[i * 16 * 8 + slot]);
-#pragma unroll
-        for (int j = 0; j < WN; ++j) wf[j] = __builtin_bit_cast(elem8_t, w[j * 16 * 8 + slot]);
+        vmvg::read_frags<Cfg>(smem, slot_idx, kk, wave_m, wave_n, frow, fgrp, fswz, af, wf);
     };
     auto mma = [&](const elem8_t (&af)[WM], const elem8_t (&wf)[WN]) {
         if constexpr (LNS) {
@@ -214,11 +194,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-                    acc[j][i] = VMV_MFMA16(wf[j], af[i], acc[j][i], 0, 0, 0);
+            mma_tile(acc, af, wf);
         }
     };
 
@@ -273,7 +249,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         constexpr bool GEGLU = decltype(geglu_tag)::value;
         constexpr int OWC = GEGLU ? 8 * WN : 16 * WN;
         constexpr int NR = (16 * (OWC / 8) + 63) / 64;
-        const int nbase = n0 + wave_n * 16 * WN + 4 * fgrp;
         {   // this wave's 16*WN bias values (and, with a folded LayerNorm, column sums) go straight into the wave's LDS strip by
             // 4-byte LDS-DMA: no registers held across the tile's last MFMAs (8 of them made <4,3,5> spill into the epilogue,
             // where every scratch reload waits out the in-order vmcnt queue), no ds_write, and columns >= N read as zero
@@ -299,7 +274,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
                     resv[i][r] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, unit_offsets(m0, n0, i, r, p.ldr, geglu_tag), sb, 0);
             }
         }
-        (void)nbase;
     };
     auto epilogue = [&](int m0, int n0, unsigned char* slot_base, auto geglu_tag) {
         constexpr bool GEGLU = decltype(geglu_tag)::value;
@@ -416,13 +390,11 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_sched_barrier(0);
-            // Store-data discipline (found with the retired wave-specialised kernel, where 168 registers make the allocator reuse registers at
-            // once): an LDS read that RETURNS into a pending buffer_store's data registers corrupts the store when the store
-            // path is backed up.  So store data is always a VALU-written copy (`sd`), never an LDS-read destination, and the
-            // previous group's `sd` is kept alive (fake use) until this group's LDS reads — bias strip, slab — have returned.
+            // Store-data discipline (gemm_glds_common.h): the stores take VALU-written copies, and the previous group's copies are kept
+            // alive until this group's LDS reads — bias strip, slab — have returned.
 #pragma unroll
             for (int r = 0; r < NR; ++r)
-                if (i > 0) asm volatile("" ::"v"(sd_prev[r]));
+                if (i > 0) keep_alive(sd_prev[r]);
             u32x4_t sd[NR];
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
@@ -434,9 +406,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
                     for (int e = 0; e < 8; ++e) a[e] += res_scale * b[e];
                     v = pack8(a);
                 }
-                asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
-                             : "=&v"(sd[r].x), "=&v"(sd[r].y), "=&v"(sd[r].z), "=&v"(sd[r].w)
-                             : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+                sd[r] = valu_copy(v);
             }
             // The slot just consumed is refilled (group i + 2) BEFORE this group's stores: vmcnt retires in order, so a load
             // issued behind stores can only be waited for together with them (a full write round trip).
@@ -482,7 +452,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
         if (!first) {                             // the previous tile's last store data stays alive until these reads returned
             __builtin_amdgcn_s_waitcnt(0xc07f);
 #pragma unroll
-            for (int r = 0; r < NR_MAX; ++r) asm volatile("" ::"v"(sd_prev[r]));
+            for (int r = 0; r < NR_MAX; ++r) keep_alive(sd_prev[r]);
         }
         // chunk consumed+1: with the 3-stage ring it was waited for before the previous epilogue; with the 2-stage ring it
         // was issued right before that epilogue, so exactly the epilogue's stores are younger than it
@@ -541,7 +511,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 1 : 2) void gemm_pglds_kernel
 template <int NWM, int WM, int WN>
 int launch_pglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
     using Cfg = PgCfg<NWM, WM, WN>;
-    static_assert(Cfg::LPT >= 6 && Cfg::LPT <= 9 && (Cfg::STAGES == 2 || 2 * Cfg::LPT <= 14), "wait_vmcnt literals");
     static_assert(Cfg::DEDICATED || (Cfg::NW * 4096 <= Cfg::STAGE_BYTES), "per-wave slabs fit in one ring slot");
     static_assert(16 * (16 * WN * 2 + 16) <= 2816 && 16 * WN * 4 <= 512 && Cfg::LDS_TOTAL <= Cfg::LDS_LIMIT, "LDS budget");
     const int tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
@@ -587,14 +556,8 @@ bool vmv_gemm_pglds_supported(const VmvGemmParams& p) {
     if (p.ksplit > 1) return false;
     for (int i = 0; i < p.nseg; ++i)
         if (p.seg[i].mode != VMV_SEG_LINEAR) return false;
-    long maxrows = p.M;
-    if (p.OH > 0) { const long src_rows = (long)(p.M / (p.OH * p.OW) + 1) * p.IH * p.IW; if (src_rows > maxrows) maxrows = src_rows; }
-    for (int i = 0; i < p.nseg; ++i)
-        if (maxrows * (long)p.seg[i].ld * 2 >= (1L << 31) - 65536) return false;
-    if ((long)p.N * p.ktot * 2 >= (1L << 31) - 65536) return false;
-    // the epilogue addresses out / residual through buffer descriptors too (32-bit byte offsets)
-    if ((long)(p.M + 256) * p.ldo * (p.out_fp32 ? 4 : 2) >= (1L << 31) - 65536) return false;
-    if (p.residual && (long)(p.M + 256) * p.ldr * 2 >= (1L << 31) - 65536) return false;
+    // 32-bit byte offsets: sources and W, and the epilogue addresses out / residual through buffer descriptors too (a tile's rows past M)
+    if (!vmv_gemm_spans32(p, vmv_gemm_src_rows(p), 0, p.M + 256, p.M + 256)) return false;
     return true;
 }
 

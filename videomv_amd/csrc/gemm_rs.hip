@@ -76,13 +76,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
 
     // ---- block -> (row tile, column split); XCD-aware bijection: the splits of one row tile run on one XCD (A comes from its L2)
     const int nblk = tiles_m * nsplit;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int logical = xcd_logical(blockIdx.x, nblk);
     const int mt = logical / nsplit, ns = logical - mt * nsplit;
     const int m_wave = mt * Cfg::BM + wave * (16 * RT);
     const int n_begin = ns * cols_per_split;
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     {
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (uint32_t)p.N * 4u : 0u, SRD_FLAGS);
         for (int q = wave; q * 256 < ncols; q += Cfg::NW)      // 256 floats per wave-instruction; columns >= N / no bias: zeros
-            VMV_BLDS16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(n_begin + q * 256 + 4 * lane) * 4u, 0);
+            blds16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(n_begin + q * 256 + 4 * lane) * 4u, 0);
     }
     // folded GroupNorm (vmv.h: gn_table): a block's rows lie in at most two consecutive stat groups (gn_rows_per_stat >= BM); their
     // scale / shift rows — 2 x 2 x K floats, contiguous in the table — go to LDS behind the bias strip, before the W ring
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
         const uint32_t nstat = (uint32_t)((p.M + p.gn_rows_per_stat - 1) / p.gn_rows_per_stat);
         const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gn_table), 0, nstat * (uint32_t)(2 * Cfg::K * 4), SRD_FLAGS);
         for (int q = wave; q * 1024 < Cfg::TAB_BYTES; q += Cfg::NW)
-            VMV_BLDS16(t_rsrc, reinterpret_cast<unsigned char*>(tab_lds) + q * 1024, (uint32_t)(gn_first * 2 * Cfg::K * 4 + q * 1024 + 16 * lane), 0);
+            blds16(t_rsrc, reinterpret_cast<unsigned char*>(tab_lds) + q * 1024, (uint32_t)(gn_first * 2 * Cfg::K * 4 + q * 1024 + 16 * lane), 0);
     }
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     auto issue_chunk = [&](int c, int slot) {
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
             const int u = wave * (P * 64) + q * 64 + ln;
             const int r = u / Cfg::SPR, s = u - r * Cfg::SPR;
             const int sw = KS == 10 ? ((r >> 1) & 7) : (r & 15);
-            VMV_BLDS16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
+            blds16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
         }
     };
     const int pro = NC < Cfg::STAGES ? NC : Cfg::STAGES;
@@ -293,7 +287,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     auto store_pair = [&](const int ocol, const int i, u32x4_t o) {
         o = swap16_xz_yw(o);
         __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, row_ok(i) ? ovo : OOB, (uint32_t)((m_wave + 16 * i) * p.ldo + ocol) * 2u, 0);
-        // Store-data discipline (cf. gemm_pglds.hip): the allocator hands the store's registers to the next row tile's
+        // Store-data discipline (cf. gemm_glds_common.h): the allocator hands the store's registers to the next row tile's
         // v_pk_add_f32 at once, and with the VALU write directly behind the store the LAST dword of the last four lanes of
         // every 16-lane row went out holding the new fp32 value (first GPU run of this kernel: every launch, rows 12-15 of a
         // tile, channels 6-7 of each 8).  The data stays live — and nothing is issued — for 8 states after the store.
@@ -453,10 +447,7 @@ bool vmv_gemm_rs_supported(const VmvGemmParams& p) {
     const int n_out = geglu ? p.N / 2 : p.N;
     if ((p.ldo & 7) || (n_out & 7) || !vmv_aligned16(p.out)) return false;
     if (p.residual && ((p.ldr & 7) || !vmv_aligned16(p.residual))) return false;
-    if ((long)(p.M + 512) * p.seg[0].ld * 2 >= (1L << 31) - 65536) return false;
-    if ((long)(p.M + 512) * p.ldo * 2 >= (1L << 31) - 65536) return false;
-    if (p.residual && (long)(p.M + 512) * p.ldr * 2 >= (1L << 31) - 65536) return false;
-    if ((long)p.N * p.ktot * 2 >= (1L << 31) - 65536) return false;
+    if (!vmv_gemm_spans32(p, p.M + 512, 0, p.M + 512, p.M + 512)) return false;      // 32-bit byte offsets, a tile's rows past M included
     RsPlan pl;
     return rs_plan(p, 0, pl, 256);
 }

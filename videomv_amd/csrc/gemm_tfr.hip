@@ -59,15 +59,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
     const int C = p.seg[0].k, F = p.F, P = p.P;
     const int NA = C >> 6;                                      // 64-channel A stages = blocks of six phases (2 k-steps x 3 taps)
 
-    // ---- XCD-aware tile mapping (bijective, as gemm_xglds.hip): the N tiles of one row tile are adjacent
-    const int nblk = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // ---- XCD-aware tile mapping (gemm_common.h): the N tiles of one row tile are adjacent
+    const int logical = xcd_logical(blockIdx.x, gridDim.x);
     const int rt = logical / tiles_n, n0 = (logical - rt * tiles_n) * TF_BN;
     const int b = rt / tiles_g, px0 = (rt - b * tiles_g) * PT;
     const int RV = F * PT;                                      // valid rows of the tile (<= 192)
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
     auto a_request = [&](const int a) {          // the three units of A stage a (channels 64 a ..) into buffer a & 1
         unsigned char* dst = abuf + (a & 1) * TF_ABYTES + TF_PAD * 128 + wave * 1024;
 #pragma unroll
-        for (int q = 0; q < 3; ++q) VMV_BLDS16(a_rsrc, dst + q * 8192, avo[q], (uint32_t)a * 128u);
+        for (int q = 0; q < 3; ++q) blds16(a_rsrc, dst + q * 8192, avo[q], (uint32_t)a * 128u);
     };
     // half-unit hu = 2 q + h (4 channels = 8 bytes) of stage a, in place: elem(silu(x * scale + shift)); zero rows stay zero.  Six of
     // them per A stage, one per MFMA half-phase (below), so that each is ~30 VALU operations beside 15 MFMAs.
@@ -136,8 +129,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
         unsigned char* wbase = smem + (t & (TF_S - 1)) * TF_WBYTES + wave * 1024;
         const uint32_t so = (uint32_t)(tap * C + ks * 32) * 2u;
 #pragma unroll
-        for (int j = 0; j < TF_NWI; ++j) VMV_BLDS16(w_rsrc, wbase + j * (TF_NW * 1024), wvo0 + (uint32_t)j * wstride, so);
-        if (xw) VMV_BLDS16(w_rsrc, wbase + TF_NWI * (TF_NW * 1024), wvo0 + (uint32_t)TF_NWI * wstride, so);
+        for (int j = 0; j < TF_NWI; ++j) blds16(w_rsrc, wbase + j * (TF_NW * 1024), wvo0 + (uint32_t)j * wstride, so);
+        if (xw) blds16(w_rsrc, wbase + TF_NWI * (TF_NW * 1024), wvo0 + (uint32_t)TF_NWI * wstride, so);
     };
 
     // ---- prologue: tables, bias, zero padding rows, A stage 0, the W ring
@@ -274,7 +267,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
         t6 = t6 == 4 ? 0 : t6 + 2;
     }
 
-    // ---- epilogue: bias, activation -> LDS staging of whole rows -> 16-byte row stores (+ residual), as gemm_xglds.hip
+    // ---- epilogue: bias, activation -> LDS staging of whole rows -> 16-byte row stores (+ residual), as gemm_glds.hip
     __syncthreads();                                            // ring / A buffers no longer read by anyone
 #pragma unroll
     for (int j = 0; j < TF_WN; ++j) {
@@ -294,7 +287,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
     uint16_t* outp = reinterpret_cast<uint16_t*>(p.out);
     const uint16_t* resp = reinterpret_cast<const uint16_t*>(p.residual);
     const float rs = p.res_scale != 0.f ? p.res_scale : 1.f;
-    u32x4_t sd_prev = u32x4_t{0u, 0u, 0u, 0u};
+    u32x4_t sd_prev = u32x4_t{0u, 0u, 0u, 0u};                  // store-data discipline (gemm_glds_common.h)
 #pragma unroll 1
     for (int idx = tid; idx < RV * U; idx += TF_NT) {
         const int r = idx / U, u = idx - r * U;
@@ -312,13 +305,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tfr_kernel(const VmvGemmParams p,
             for (int e = 0; e < 8; ++e) a[e] += rs * c[e];
             v = pack8(a);
         }
-        // store-data discipline (gemm_pglds.hip): the stored registers are a VALU-written copy, kept alive past the next LDS read
         __builtin_amdgcn_s_waitcnt(0xc07f);
-        asm volatile("" ::"v"(sd_prev));
-        u32x4_t sd;
-        asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
-                     : "=&v"(sd.x), "=&v"(sd.y), "=&v"(sd.z), "=&v"(sd.w)
-                     : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+        keep_alive(sd_prev);
+        const u32x4_t sd = valu_copy(v);
         *reinterpret_cast<u32x4_t*>(outp + m * p.ldo + n) = sd;
         sd_prev = sd;
     }
@@ -340,7 +329,7 @@ bool vmv_gemm_tfr_supported(const VmvGemmParams& p) {
     if (p.epilogue != VMV_EPI_NONE || p.rowvec || p.rowstat || p.colsum || p.ln_eps > 0.f || p.wgroup_rows || p.ksplit > 1 || p.out_fp32) return false;
     if ((p.ldo & 7) || !vmv_aligned16(p.out) || (p.residual && ((p.ldr & 7) || !vmv_aligned16(p.residual)))) return false;
     if (p.gn_table && (p.gn_rows_per_stat != p.F * p.P || !vmv_aligned16(p.gn_table))) return false;
-    if ((long)p.M * s0.ld * 2 >= (1L << 31) - 65536 || (long)(p.N + TF_BN) * p.ktot * 2 >= (1L << 31) - 65536) return false;
+    if (!vmv_gemm_spans32(p, p.M, TF_BN, 0, 0)) return false;      // 32-bit byte offsets: the source, W with a tile's rows past N
     return true;
 }
 

@@ -91,13 +91,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
     //      A block re-loads its rows only when its range crosses a tile boundary (at most twice more); W keeps streaming through the
     //      ring across items: chunk c of the block is section c % 3 (q, k, v) of head (i0 + c / 3) % heads.
     const int nblk = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int logical = xcd_logical(blockIdx.x, nblk);
     const long nitems = (long)ntiles * heads;
     const int i0 = (int)(((long)logical * nitems) / nblk), i1 = (int)(((long)(logical + 1) * nitems) / nblk);
     const int nit = i1 - i0;                                    // >= 1 (the grid never exceeds the item count)
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
     {
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (uint32_t)p.N * 4u : 0u, SRD_FLAGS);
         for (int q = wave; q * 256 < p.N; q += TQ_NW)
-            VMV_BLDS16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
+            blds16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
     }
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     auto issue_chunk = [&](int c, int slot) {
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
             const int u = wave * (P * 64) + q * 64 + ln;
             const int r = u / TQ_SPR, s = u - r * TQ_SPR;
             const int sw = (r >> 1) & 7;
-            VMV_BLDS16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
+            blds16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
         }
     };
     const int NC = 3 * nit;
@@ -399,8 +393,7 @@ bool vmv_gemm_tqa_supported(const VmvGemmParams& p) {
     if (p.colsum && !(p.ln_eps > 0.f)) return false;
     if (!(p.epi_scale > 0.f)) return false;
     if ((p.ldo & 7) || (p.ldo < p.N / 3) || !vmv_aligned16(p.out)) return false;
-    if ((long)(p.M + 512) * p.seg[0].ld * 2 >= (1L << 31) - 65536 || (long)(p.M + 512) * p.ldo * 2 >= (1L << 31) - 65536) return false;
-    if ((long)p.N * p.ktot * 2 >= (1L << 31) - 65536) return false;
+    if (!vmv_gemm_spans32(p, p.M + 512, 0, p.M + 512, 0)) return false;      // 32-bit byte offsets, a tile's rows past M included
     return true;
 }
 

@@ -72,29 +72,9 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = WNV == 2 ? wave >> 1 : wave, wave_n = WNV == 2 ? wave & 1 : 0;
 
-    // ---- XCD-aware tile mapping (bijective, as gemm_glds.hip)
-    const int nblk = tiles_m * tiles_n;
-    int logical;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    // Round 6 — which tiles run TOGETHER on an XCD decides what its 4-MB L2 can share.  With the N tiles of one row tile adjacent, the
-    // 32 CUs of an XCD work on ONE row tile and 32 different W slices: A is shared, every W slice streams in from the fabric once PER
-    // ROW TILE (profiles/r6_gemm_traffic_by_kernel.tsv: the 7680 x 10240 x 1280 GEGLU fetches 834 MB for 46 MB of operands = W x 30 row
-    // tiles).  Grouped order (gm > 1): consecutive logical ids walk gm row tiles, then the next N tile — 32 concurrent blocks cover
-    // gm row tiles x 32 / gm column tiles, so a W slice is fetched once per gm row tiles and an A slice once per 32 / gm column tiles.
+    // ---- XCD-aware tile mapping, grouped order (gemm_common.h)
     int tm_, tn_;
-    if (gm > 1) {
-        const int gsz = gm * tiles_n, g = logical / gsz, first = g * gm;
-        const int gmh = tiles_m - first < gm ? tiles_m - first : gm;
-        const int rem = logical - g * gsz;
-        tn_ = rem / gmh; tm_ = first + (rem - tn_ * gmh);
-    } else {
-        tm_ = logical / tiles_n; tn_ = logical - tm_ * tiles_n;
-    }
+    tile_of_block(blockIdx.x, tiles_m, tiles_n, gm, tm_, tn_);
     const int m0 = tm_ * BM, n0 = tn_ * BN;
 
     // ---- loader.  A wave instruction covers 16 rows x 64 B; lane -> (row in group = lane >> 2, physical 16-B slot = lane & 3).
@@ -150,8 +130,6 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
         const bool tappable = (mode == VMV_SEG_SPATIAL && p.stride == 1 && p.ups == 0) || mode == VMV_SEG_TEMPORAL;
         if (!SK && tapmajor && tappable)
             while (s + run_len < p.nseg && run_len < 15 && seg_same(p.seg[s + run_len], s0)) ++run_len;
-        // (segment fields are read in wave-uniform control flow: inside per-row branches the compiler copied the whole kernel-argument
-        //  segment table to scratch to index it)
         const bool single = run_len == 1;
         // (the segment table is read in wave-uniform code only — tap loop outside, rows inside: indexed from inside the per-row code the
         //  compiler copies the whole kernel-argument table to scratch)
@@ -235,11 +213,11 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
         const uint32_t a_so = (uint32_t)kc * 2u, w_so = (uint32_t)(koff + run_t * sg.k + kc) * 2u, d2 = (uint32_t)(delta * 2);
 #pragma unroll
         for (int i = 0; i < Cfg::NAI; ++i)
-            VMV_BLDS16(a_rsrc, abase + i * (NW * 1024), (kvalid && ((rmask[i >> 1] >> (16 * (i & 1) + run_t)) & 1u)) ? avo[i] + d2 : OOB, a_so);
+            blds16(a_rsrc, abase + i * (NW * 1024), (kvalid && ((rmask[i >> 1] >> (16 * (i & 1) + run_t)) & 1u)) ? avo[i] + d2 : OOB, a_so);
 #pragma unroll
-        for (int j = 0; j < Cfg::NWI; ++j) VMV_BLDS16(w_rsrc, wbase + j * (NW * 1024), kvalid ? wvo0 + (uint32_t)j * wstride : OOB, w_so);
+        for (int j = 0; j < Cfg::NWI; ++j) blds16(w_rsrc, wbase + j * (NW * 1024), kvalid ? wvo0 + (uint32_t)j * wstride : OOB, w_so);
         if (Cfg::NWX > 0 && wave < Cfg::NWX)
-            VMV_BLDS16(w_rsrc, wbase + Cfg::NWI * (NW * 1024), kvalid ? wvo0 + (uint32_t)Cfg::NWI * wstride : OOB, w_so);
+            blds16(w_rsrc, wbase + Cfg::NWI * (NW * 1024), kvalid ? wvo0 + (uint32_t)Cfg::NWI * wstride : OOB, w_so);
         if (++run_t == run_len) {
             run_t = 0;
             if (++run_c == run_nch) {
@@ -292,8 +270,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
 #pragma unroll
     for (int i = 0; i < S; ++i) { issue(i); ++issued; }
     const bool xw = Cfg::NWX > 0 && wave < Cfg::NWX;          // this wave issues LPT + 1 loads per chunk (uniform)
-    if (xw) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 1) * (Cfg::LPT + 1)) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 1) * Cfg::LPT) : "memory");      // chunk 0 landed (mine)
+    if (xw) wait_vmcnt<(S - 1) * (Cfg::LPT + 1)>(); else wait_vmcnt<(S - 1) * Cfg::LPT>();      // chunk 0 landed (mine)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     prefetch_phase(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -315,8 +292,8 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
         if (t + 1 < nsteps) {
             // steady state: chunks t + 2, t + 3 stay in flight; in the tail (nothing left to issue) simply drain
             if (t + S > nsteps) wait_vmcnt<0>();
-            else if (xw) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 2) * (Cfg::LPT + 1)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 2) * Cfg::LPT) : "memory");
+            else if (xw) wait_vmcnt<(S - 2) * (Cfg::LPT + 1)>();
+            else wait_vmcnt<(S - 2) * Cfg::LPT>();
             __builtin_amdgcn_s_waitcnt(0xc07f);               // my fragment reads of slot st are done
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -456,8 +433,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             }
         }
         __syncthreads();
-        // Store-data discipline (see gemm_pglds.hip): the stored registers are a VALU-written copy, never the destination of an
-        // LDS read, and the previous iteration's copy stays alive until this iteration's LDS read has returned.
+        // store-data discipline (gemm_glds_common.h)
         u32x4_t sd_prev = u32x4_t{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -475,40 +451,22 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
                 if (it + RD < ITER) rr[it % RD] = res_request(hh, it + RD);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
-            asm volatile("" ::"v"(sd_prev));
-            u32x4_t sd;
-            asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
-                         : "=&v"(sd.x), "=&v"(sd.y), "=&v"(sd.z), "=&v"(sd.w)
-                         : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+            keep_alive(sd_prev);
+            const u32x4_t sd = valu_copy(v);
             *reinterpret_cast<u32x4_t*>(outp + (size_t)m * p.ldo + n) = sd;
             sd_prev = sd;
         }
     }
 }
 
-// rows of the tile group that shares W slices in an XCD's L2 (kernel header): minimises the bytes 32 concurrent blocks pull in,
-// gm x BM + 32 / gm x BN per K chunk, with 32 / gm <= the N tiles there are; 1 = the round-5 order.
-int xglds_group_m(int tiles_m, int tiles_n, int BM, int BN, int conc = 32) {
-    if (tiles_n < 2 || tiles_m < 2) return 1;
-    int best = 1, best_cost = BM + conc * BN;          // conc = blocks an XCD runs at once (32 CUs x blocks per CU)
-    for (int gm = 2; gm <= conc; gm *= 2) {
-        const int gn = (conc + gm - 1) / gm;
-        if (gn > tiles_n || gm > tiles_m) continue;
-        const int cost = gm * BM + gn * BN;
-        if (cost < best_cost) { best = gm; best_cost = cost; }
-    }
-    return best;
-}
-
 template <int NH, int WH, int EPI = 0, int WNV = 2>
-int launch_xglds(const VmvGemmParams& p, int total_steps, hipStream_t st) {
+int launch_xglds(const VmvGemmParams& p, hipStream_t st) {
     using Cfg = WgCfg<NH, WH, WNV>;
     const int tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
     const int tiles_n = (p.N + Cfg::BN - 1) / Cfg::BN;
-    const int gm = xglds_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN);
-    int nsteps = 0;                                          // chunks of WBK = 32 (total_steps counts the other kernels' 64)
+    const int gm = gemm_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, 32);
+    int nsteps = 0;                                          // chunks of WBK = 32 (vmv_gemm counts the other kernels' 64)
     for (int i = 0; i < p.nseg; ++i) nsteps += (p.seg[i].k + WBK - 1) / WBK;
-    (void)total_steps;
     if (nsteps < Cfg::STAGES || (nsteps & 1)) return VMV_GLDS_UNSUPPORTED;
     if (p.rowvec && (Cfg::BM - 1) / p.rowvec_div + 2 > Cfg::XG_MAXG) return VMV_GLDS_UNSUPPORTED;      // column vectors staged per row group
     if (p.ksplit > 1) {
@@ -549,24 +507,20 @@ int vmv_gemm_xglds_launch(const VmvGemmParams& p, int total_steps, int tile, hip
     if (vmv_gemm_ln_inline(p) || !vmv_gemm_xglds_epi_ok(p, tile)) return VMV_GLDS_UNSUPPORTED;
     const bool geglu = p.epilogue == VMV_EPI_GEGLU, lnf = p.rowstat != nullptr;
     if (p.ksplit > 1 && (geglu || lnf || !p.workspace)) return VMV_GLDS_UNSUPPORTED;      // split-K: plain epilogue only (the reduce pass runs it)
-    long maxrows = p.M;
-    if (p.OH > 0) { const long src_rows = (long)(p.M / (p.OH * p.OW) + 1) * p.IH * p.IW; if (src_rows > maxrows) maxrows = src_rows; }
-    for (int i = 0; i < p.nseg; ++i)
-        if (maxrows * (long)p.seg[i].ld * 2 >= (1L << 31) - 65536) return VMV_GLDS_UNSUPPORTED;
-    if ((long)(p.N + 320) * p.ktot * 2 >= (1L << 31) - 65536) return VMV_GLDS_UNSUPPORTED;
+    // 32-bit byte offsets: every segment's source, W with the widest tile's rows past N, the residual's rows (buffer loads)
+    if (!vmv_gemm_spans32(p, vmv_gemm_src_rows(p), 320, 0, p.M)) return VMV_GLDS_UNSUPPORTED;
     if (p.OH > 0 && (p.OH >= 32768 || p.OW >= 32768)) return VMV_GLDS_UNSUPPORTED;      // (oy, ox) packed in one register
-    if (p.residual && (long)p.M * p.ldr * 2 >= (1L << 31) - 65536) return VMV_GLDS_UNSUPPORTED;      // residual rows by 32-bit buffer offsets
     const int No = geglu ? p.N / 2 : p.N;
     if (p.ksplit <= 1 && (p.out_fp32 || (p.ldo & 7) || (No & 7) || !vmv_aligned16(p.out) ||
                           (p.residual && ((p.ldr & 7) || !vmv_aligned16(p.residual))))) return VMV_GLDS_UNSUPPORTED;   // staged epilogue only
     if (geglu || lnf) {
-        if (geglu && lnf) return launch_xglds<2, 4, XE_GEGLU | XE_LN>(p, total_steps, st);
-        if (geglu) return launch_xglds<2, 4, XE_GEGLU>(p, total_steps, st);
-        return launch_xglds<2, 4, XE_LN>(p, total_steps, st);
+        if (geglu && lnf) return launch_xglds<2, 4, XE_GEGLU | XE_LN>(p, st);
+        if (geglu) return launch_xglds<2, 4, XE_GEGLU>(p, st);
+        return launch_xglds<2, 4, XE_LN>(p, st);
     }
-    if (tile == VMV_TILE_X256x320) return launch_xglds<2, 5>(p, total_steps, st);
-    if (tile == VMV_TILE_X256x256) return launch_xglds<2, 4>(p, total_steps, st);
-    if (tile == VMV_TILE_X256x128) return launch_xglds<1, 4>(p, total_steps, st);
-    if (tile == VMV_TILE_X512x128) return launch_xglds<2, 4, 0, 1>(p, total_steps, st);
+    if (tile == VMV_TILE_X256x320) return launch_xglds<2, 5>(p, st);
+    if (tile == VMV_TILE_X256x256) return launch_xglds<2, 4>(p, st);
+    if (tile == VMV_TILE_X256x128) return launch_xglds<1, 4>(p, st);
+    if (tile == VMV_TILE_X512x128) return launch_xglds<2, 4, 0, 1>(p, st);
     return VMV_EINVAL;
 }
