@@ -147,6 +147,21 @@ typedef struct {
     int32_t gn_silu;
     /* VMV_EPI_TATTN: the softmax scale (1 / sqrt(head_dim) = 0.125); ignored by every other epilogue.  (ABI 10) */
     float epi_scale;
+    /* Nearest-x2 up-sampling + 3 x 3 convolution as FOUR 2 x 2 convolutions, one per output phase (Upsample, util.py:595-606), in one
+     * launch.  After nearest x2 the 3 x 3 window of output pixel (2i + py, 2j + px) covers 2 x 2 distinct source pixels — rows {i - 1, i}
+     * for py = 0, {i, i + 1} for py = 1, columns alike — so the weights that meet one source pixel are summed ONCE by the host
+     * (packing.pack_conv3x3_up4) and K is 4 C instead of 9 C.  phased = 1 is valid only with ups == 1, stride == 1, 16-bit output, ONE source
+     * in exactly four VMV_SEG_SPATIAL segments whose (d0, d1) are (-1,-1), (-1,0), (0,-1), (0,0) in this order, ktot = 4 k, OH = 2 IH,
+     * OW = 2 IW, and no residual, rowvec, GEGLU, folded LayerNorm / GroupNorm, grouped weights or split-K; vmv_gemm answers VMV_EINVAL to
+     * everything else that sets the field.  Semantics:
+     *   M = 4 Mp, Mp = images * IH * IW; GEMM row m = ph * Mp + r with ph = 2 py + px and r = (n IH + i) IW + j;
+     *   segment (d0, d1) of row m reads source pixel (i + py + d0, j + px + d1) of image n — source row r + (py + d0) IW + px + d1 —
+     *     and zero outside [0, IH) x [0, IW);
+     *   W = four [N][ktot] matrices, phase ph at W + ph * N * ktot elements; bias [N] as in every other mode;
+     *   GEMM row m is written to output row (n OH + 2i + py) OW + 2j + px = 4r - 2j + py OW + px.
+     * Served by the wide-tile kernel (VMV_TILE_X256x320 / X256x256 / X256x128; VMV_EINVAL for other forced tiles).  Ask
+     * vmv_gemm_up4_ok() whether to record this form or the nine-tap one (ups = 1, phased = 0).  (additive: ABI 11)                */
+    int32_t phased;
 } VmvGemmParams;
 
 #define VMV_TILE_AUTO     0
@@ -201,6 +216,9 @@ int vmv_gemm(const VmvGemmParams* p, void* stream);
 /* 1 if the host should record ONE VMV_EPI_TATTN launch for *p (a fused q | k | v + temporal-attention GEMM, epilogue already set)
  * instead of the q | k | v GEMM + vmv_attention pair: the fused kernel supports the shape and its grid fills the chip */
 int vmv_gemm_tqa_ok(const VmvGemmParams* p);
+/* 1 if the host should record *p — a complete phased block (VmvGemmParams.phased = 1, tile = VMV_TILE_AUTO) — instead of the nine-tap
+ * nearest-x2 convolution: vmv_gemm accepts it and every phase has at least VMV_UP4_MIN_ROWS rows (environment, read at every call: record time only; default 769 = more than three 256-row tiles) */
+int vmv_gemm_up4_ok(const VmvGemmParams* p);
 /* 1 if vmv_gemm accepts *p (rowstat ignored) with in-loop LayerNorm statistics (VmvGemmParams.ln_eps), else 0 */
 int vmv_gemm_ln_inline_ok(const VmvGemmParams* p);
 /* 1 if vmv_gemm would run *p (tile = VMV_TILE_AUTO) on the row-stationary kernel, which takes the statistics of a folded

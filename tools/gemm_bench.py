@@ -42,12 +42,21 @@ def main():
         # VAE decoder levels at 24 frames of 320 x 512 (decode_views takes all frames in one plan)
         ("vae conv 512 @80x128", 24 * 80 * 128, 512, 512, "conv"), ("vae conv 256 @160x256", 24 * 160 * 256, 256, 256, "conv"),
         ("vae conv 128 @320x512", 24 * 320 * 512, 128, 128, "conv"),
+        # the UNet decoder's Upsample convolutions (nearest x2 + 3x3; M = OUTPUT rows, C = input channels): up9 = the nine-tap gather over
+        # the up-sampled image, up4 = four 2x2 phase convolutions with pre-summed weights (vmv.h VmvGemmParams.phased; wide tiles only);
+        # these lines also print the launch time, since the two forms do different amounts of arithmetic
+        ("up9 L1->L0 640", M0, 640, 640, "up9"), ("up4 L1->L0 640", M0, 640, 640, "up4"),
+        ("up9 L2->L1 1280", M1, 1280, 1280, "up9"), ("up4 L2->L1 1280", M1, 1280, 1280, "up4"),
+        ("up9 L3->L2 1280", M2, 1280, 1280, "up9"), ("up4 L3->L2 1280", M2, 1280, 1280, "up4"),
+        ("up9 L1->L0 640 @32x32", 49152, 640, 640, "up9"), ("up4 L1->L0 640 @32x32", 49152, 640, 640, "up4"),
+        ("up9 L2->L1 1280 @32x32", 12288, 1280, 1280, "up9"), ("up4 L2->L1 1280 @32x32", 12288, 1280, 1280, "up4"),
+        ("up9 L3->L2 1280 @32x32", 3072, 1280, 1280, "up9"), ("up4 L3->L2 1280 @32x32", 3072, 1280, 1280, "up4"),
     ]
     flt = os.environ.get("VMV_BENCH_SHAPES", "")
     for name, M, N, C, kind in shapes:
         if flt and not any(f in name for f in flt.split(",")):
             continue
-        x = torch.randn(M, C, device=dev).to(BF)
+        x = torch.randn(M // 4 if kind in ("up9", "up4") else M, C, device=dev).to(BF)
         kw = {}
         No = N
         if kind in ("lin", "linres", "geglu", "lnlin", "lngeglu"):
@@ -68,9 +77,15 @@ def main():
             hw = {M0: (40, 64), M1: (20, 32), M2: (10, 16), 1920: (5, 8), 24 * 80 * 128: (80, 128), 24 * 160 * 256: (160, 256),
                   24 * 320 * 512: (320, 512)}[M]
             geom = ops.Geom(OH=hw[0], OW=hw[1], IH=hw[0], IW=hw[1])
+        elif kind in ("up9", "up4"):
+            K = (9 if kind == "up9" else 4) * C
+            segs = ops.conv3x3_segs([(x, C, C)]) if kind == "up9" else ops.up4_segs(x, C, C)
+            oh, ow = {M0: (40, 64), M1: (20, 32), M2: (10, 16), 49152: (32, 32), 12288: (16, 16), 3072: (8, 8)}[M]
+            geom = ops.Geom(OH=oh, OW=ow, IH=oh // 2, IW=ow // 2, stride=1, ups=1)
+            kw["phased"] = kind == "up4"
         else:
             K = 3 * C; segs = ops.temporal_segs(x, C, C); geom = ops.Geom(F=24, P=M // 48)
-        w = (torch.randn(N, K, device=dev) * K ** -0.5).to(BF)
+        w = (torch.randn((4 if kind == "up4" else 1) * N, K, device=dev) * K ** -0.5).to(BF)
         b = torch.randn(N, device=dev)
         out = torch.empty(M, No, device=dev, dtype=BF)
         if kind == "linres":
@@ -82,7 +97,9 @@ def main():
                 line += "      -    "; continue
             if tile in (L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128) and (kind in ("geglu", "lngeglu", "lnlin") or (tile == L.TILE_X256x320 and N % 320)):
                 line += "      -    "; continue
-            if tile in (L.TILE_RS, L.TILE_RS512, L.TILE_RS256) and (kind in ("conv", "tconv") or C not in (320, 640) or (tile == L.TILE_RS512 and C != 320)):
+            if kind == "up4" and tile not in (0, L.TILE_X256x320, L.TILE_X256x256, L.TILE_X256x128):
+                line += "      -    "; continue
+            if tile in (L.TILE_RS, L.TILE_RS512, L.TILE_RS256) and (kind in ("conv", "tconv", "up9", "up4") or C not in (320, 640) or (tile == L.TILE_RS512 and C != 320)):
                 line += "      -    "; continue
             ws = None
             ks = int(os.environ.get("VMV_BENCH_KSPLIT", "0"))
@@ -91,7 +108,7 @@ def main():
                 kw["ksplit"] = ks
             p = ops.gemm_params(M, N, segs, w, out, No, bias=b, geom=geom, tile=tile, workspace=ws, **kw)
             ms = bench(lambda: S.gemm(p))
-            line += f" t{tile}:{2.0 * M * N * K / ms / 1e9:7.1f}"
+            line += f" t{tile}:{2.0 * M * N * K / ms / 1e9:7.1f}" + (f" ({1000.0 * ms:6.1f} us)" if kind in ("up9", "up4") else "")
         print(line, flush=True)
 
 

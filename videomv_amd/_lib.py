@@ -76,7 +76,8 @@ class GemmParams(C.Structure):
                 ("ksplit", C.c_int32), ("workspace", C.c_void_p),
                 ("tile", C.c_int32), ("res_scale", C.c_float), ("rowstat", C.c_void_p), ("colsum", C.c_void_p),
                 ("ln_eps", C.c_float), ("wgroup_rows", C.c_int32), ("wgroup_stride", C.c_int64),
-                ("gn_table", C.c_void_p), ("gn_rows_per_stat", C.c_int32), ("gn_silu", C.c_int32), ("epi_scale", C.c_float)]
+                ("gn_table", C.c_void_p), ("gn_rows_per_stat", C.c_int32), ("gn_silu", C.c_int32), ("epi_scale", C.c_float),
+                ("phased", C.c_int32)]
 
 
 class GroupNormParams(C.Structure):
@@ -184,6 +185,7 @@ SYMBOLS = {
     "vmv_gemm_rs_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "vmv_gemm_tfr_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "vmv_gemm_tqa_ok": (C.c_int, [C.POINTER(GemmParams)]),
+    "vmv_gemm_up4_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "vmv_has_experiments": (C.c_int, []),
     "vmv_ff_fused": (C.c_int, [C.POINTER(FfParams), _P]),
     "vmv_ff_fused_ok": (C.c_int, [C.POINTER(FfParams)]),

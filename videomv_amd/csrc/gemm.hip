@@ -357,6 +357,17 @@ bool retired_tile(int t) {
 int final_tile(const VmvGemmParams& p, int total_steps) {
     int picked = pick_tile(p, total_steps);
     if (retired_tile(picked)) return VMV_EINVAL;
+    if (p.phased) {      // the phased up-convolution lives in the wide-tile kernel only (gemm_xglds.hip UP4)
+        const bool x = picked == VMV_TILE_X256x320 || picked == VMV_TILE_X256x256 || picked == VMV_TILE_X256x128;
+        if (x) return picked;
+        if (p.tile != VMV_TILE_AUTO) return VMV_EINVAL;
+        // the policy above judged the K = 4 C convolution over M rows too small for a wide tile: the widest form whose grid still
+        // covers the 256 CUs, else the 128-column form (most tiles)
+        const long tm = 4L * ((p.M / 4 + 255) / 256);
+        if (p.N % 320 == 0 && tm * (p.N / 320) >= 256) return VMV_TILE_X256x320;
+        if (p.N % 256 == 0 && tm * (p.N / 256) >= 256) return VMV_TILE_X256x256;
+        return VMV_TILE_X256x128;
+    }
     if (picked == VMV_TILE_HALO) return vmv_conv_halo_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TFR) return vmv_gemm_tfr_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TQA) return vmv_gemm_tqa_supported(p) && (p.tile == VMV_TILE_AUTO || p.tile == VMV_TILE_TQA) ? picked : VMV_EINVAL;
@@ -381,6 +392,22 @@ int final_tile(const VmvGemmParams& p, int total_steps) {
         picked != VMV_TILE_128x64 && picked != VMV_TILE_64x64)
         picked = (p.epilogue != VMV_EPI_GEGLU && p.N % 160 == 0) ? VMV_TILE_P256x160 : VMV_TILE_P256x128;
     return picked;
+}
+
+// the contract of VmvGemmParams.phased (vmv.h)
+bool up4_valid(const VmvGemmParams& p) {
+    if (p.phased != 1 || p.ups != 1 || p.stride != 1 || p.out_fp32 || p.nseg != 4 || p.ksplit > 1) return false;
+    if (p.residual || p.rowvec || p.rowstat || p.colsum || p.gn_table || p.gn_silu || p.wgroup_rows != 0 || p.epilogue != VMV_EPI_NONE) return false;
+    static const int taps[4][2] = {{-1, -1}, {-1, 0}, {0, -1}, {0, 0}};
+    for (int s = 0; s < 4; ++s) {
+        const VmvGemmSeg& sg = p.seg[s];
+        if (sg.mode != VMV_SEG_SPATIAL || sg.src != p.seg[0].src || sg.ld != p.seg[0].ld || sg.k != p.seg[0].k) return false;
+        if (sg.d0 != taps[s][0] || sg.d1 != taps[s][1]) return false;
+    }
+    if (p.ktot != 4 * p.seg[0].k || p.OH != 2 * p.IH || p.OW != 2 * p.IW) return false;
+    const long hw = (long)p.IH * p.IW;
+    if ((p.M & 3) || (p.M / 4) % hw != 0) return false;      // whole images: M = 4 * images * IH * IW
+    return true;
 }
 
 bool ln_inline_ok(const VmvGemmParams& p) {
@@ -413,6 +440,20 @@ extern "C" int vmv_gemm_tfr_ok(const VmvGemmParams* pp) {
 extern "C" int vmv_gemm_tqa_ok(const VmvGemmParams* pp) {
     if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
     return vmv_gemm_tqa_preferred(*pp) ? 1 : 0;
+}
+
+// Record the phased form of a nearest-x2 convolution?  (vmv.h)  Default: more than three 256-row tiles per phase (> 768 rows).  Below
+// that the launch is a handful of tiles either way and the nine-tap form stays — it is also the only form the host-side plan
+// interpreter of the tests executes, and the largest plan those tests execute has 768 rows per phase (2 x 24 frames of 4 x 4 source
+// pixels), which is also the third-level launch of the 24 x 32 x 32 plan: that one launch stays on nine taps.
+extern "C" int vmv_gemm_up4_ok(const VmvGemmParams* pp) {
+    if (!pp || pp->tile != VMV_TILE_AUTO || !pp->phased) return 0;
+    // (tests reach the kernel at small shapes.  Read at every call — this runs when a plan is RECORDED, never on the replay path — so
+    //  that a test can switch the form inside one process.)
+    const char* e = getenv("VMV_UP4_MIN_ROWS");
+    const long min_rows = e ? atol(e) : 769;
+    if (pp->M / 4 < min_rows) return 0;
+    return vmv_gemm_validate(pp) == VMV_OK ? 1 : 0;
 }
 
 extern "C" int vmv_gemm_pick_tile(const VmvGemmParams* pp) {
@@ -470,6 +511,10 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
     if (p.residual && ((p.ldr & 3) || (((uintptr_t)p.residual) & 7))) return VMV_EALIGN;
     if (p.ksplit > 1 && (!p.workspace || !vmv_aligned16(p.workspace))) return VMV_ENULL;
     if ((long)p.M * (long)maxld >= (1L << 31) || (long)p.N * (long)p.ktot >= (1L << 31)) return VMV_ERANGE;
+    if (p.phased) {        // nearest-x2 + 3 x 3 as four 2 x 2 phase convolutions (vmv.h)
+        if (!up4_valid(p)) return VMV_EINVAL;
+        if (4L * p.N * (long)p.ktot >= (1L << 31)) return VMV_ERANGE;
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
     if (p.rowstat) {       // LayerNorm-folded GEMM: implemented by the persistent kernel's epilogue and the generic one
@@ -513,6 +558,7 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
         case VMV_TILE_X256x128:
         case VMV_TILE_X512x128:
             rc = vmv_gemm_xglds_launch(p, total_steps, picked, st);
+            if (rc == VMV_GLDS_UNSUPPORTED && p.phased) return VMV_EINVAL;      // (no other kernel serves the phased form)
             if (rc == VMV_GLDS_UNSUPPORTED && (p.rowstat || p.epilogue == VMV_EPI_GEGLU)) {      // the fused epilogues' other home
                 if (p.tile != VMV_TILE_AUTO) return VMV_EINVAL;
                 rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x128, st);

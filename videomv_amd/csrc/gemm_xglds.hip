@@ -59,7 +59,13 @@ constexpr int XE_GEGLU = 1, XE_LN = 2;       // EPI bits
 // what is left; the launcher keeps every split even and >= STAGES) and writes its raw fp32 accumulators to slab blockIdx.y of
 // p.workspace; gemm_splitk_reduce (gemm.hip) sums the slabs and runs the epilogue.  For the grids that cannot fill the chip with
 // 256-row wide tiles on their own (the fourth UNet level, a frame-parallel rank's M / 8 rows) without falling back to 128-row tiles.
-template <int NH, int WH, int EPI = 0, bool SK = false, int WNV = 2>
+// UP4: the phased nearest-x2 + 3 x 3 convolution (vmv.h: VmvGemmParams.phased) — four 2 x 2 convolutions, one per output phase
+// (py, px), in one launch.  The row-tile axis holds the four phases one after the other (tiles_m = 4 x the tiles of one phase's Mp = M / 4
+// rows: a tile never straddles two phases, the last tile of each phase is ragged); the phase is block-uniform.  A tile's rows are the
+// SOURCE pixels r = (n IH + i) IW + j; with the origin shifted to (i + py, j + px) the four taps (d0, d1) in {-1, 0}^2 are a run of the
+// tap-interleaved walk exactly as a stride-1 convolution's (one base offset per row, a validity bit per tap, a wave-uniform delta);
+// W is the phase's own [N][ktot] matrix; the staged store loop writes row r to output row 4 r - 2 j + py OW + px.
+template <int NH, int WH, int EPI = 0, bool SK = false, int WNV = 2, bool UP4 = false>
 __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams p, const int tiles_m, const int tiles_n, const int nsteps_arg,
                                                             const int nsteps_total, const int gm, const int tapmajor) {
     VMV_KERNEL_ENTER();
@@ -75,7 +81,12 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     // ---- XCD-aware tile mapping, grouped order (gemm_common.h)
     int tm_, tn_;
     tile_of_block(blockIdx.x, tiles_m, tiles_n, gm, tm_, tn_);
-    const int m0 = tm_ * BM, n0 = tn_ * BN;
+    static_assert(!UP4 || (!SK && EPI == 0 && WNV == 2), "phased up-convolution: plain epilogue, no split-K");
+    // UP4: m0 / Mrows count rows INSIDE the block's phase (scalar registers: tm_ is block-uniform)
+    const int tiles_ph = UP4 ? tiles_m >> 2 : tiles_m;
+    const int ph = UP4 ? __builtin_amdgcn_readfirstlane(tm_ / tiles_ph) : 0;
+    const int m0 = (UP4 ? tm_ - ph * tiles_ph : tm_) * BM, n0 = tn_ * BN;
+    const int Mrows = UP4 ? p.M >> 2 : p.M;
 
     // ---- loader.  A wave instruction covers 16 rows x 64 B; lane -> (row in group = lane >> 2, physical 16-B slot = lane & 3).
     //      Row r keeps logical k-slot s at s ^ T[(r >> 2) & 3], T = {0, 2, 3, 1}: ds_read_b128 serves a wave in four groups
@@ -88,7 +99,10 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     const int lsw = (lane & 3) ^ ((0x78 >> (2 * ((lane >> 4) & 3))) & 3);
     // weights: this lane's row of W group j is n0 + (j NW + wave) 16 + lrow — linear in j, so ONE offset register; rows >= N
     // fall outside the descriptor and read as zero
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
+    // (UP4: four matrices, the phase's at W + ph N ktot elements)
+    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(p.W)) + (UP4 ? (size_t)ph * (size_t)p.N * (size_t)p.ktot * 2u : (size_t)0), 0,
+        (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     const uint32_t wvo0 = (uint32_t)((n0 + wave * 16 + lrow) * p.ktot + lsw * 8) * 2u;
     const uint32_t wstride = (uint32_t)(NW * 16 * p.ktot) * 2u;
 
@@ -127,7 +141,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
         const VmvGemmSeg& s0 = p.seg[s];
         run_nch = (s0.k + WBK - 1) / WBK;
         const int mode = s0.mode, ld = s0.ld;
-        const bool tappable = (mode == VMV_SEG_SPATIAL && p.stride == 1 && p.ups == 0) || mode == VMV_SEG_TEMPORAL;
+        const bool tappable = UP4 || (mode == VMV_SEG_SPATIAL && p.stride == 1 && p.ups == 0) || mode == VMV_SEG_TEMPORAL;
         if (!SK && tapmajor && tappable)
             while (s + run_len < p.nseg && run_len < 15 && seg_same(p.seg[s + run_len], s0)) ++run_len;
         const bool single = run_len == 1;
@@ -141,7 +155,13 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             int m = m0 + (i * NW + wave) * 16 + lrow;
             asm volatile("" : "+v"(m));                 // not loop-invariant as far as the compiler can tell: see above
             nb[i] = 0; oy[i] = 0; ox[i] = 0; mask[i] = 0;
-            if (mode == VMV_SEG_SPATIAL) {
+            if constexpr (UP4) {                        // source pixel (i, j) of row m; the taps' origin is (i + py, j + px)
+                const int hw = p.IH * p.IW;
+                const int n = m / hw, rem = m - n * hw;
+                const int iy = rem / p.IW;
+                oy[i] = iy + (ph >> 1); ox[i] = rem - iy * p.IW + (ph & 1);
+                nb[i] = n * hw;
+            } else if (mode == VMV_SEG_SPATIAL) {
                 const int hw = p.OH * p.OW;
                 const int n = m / hw, rem = m - n * hw;
                 oy[i] = rem / p.OW; ox[i] = rem - oy[i] * p.OW;
@@ -149,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             } else if (mode == VMV_SEG_TEMPORAL) {
                 nb[i] = (m / p.P) % p.F;
             }
-            inm[i] = m < p.M;
+            inm[i] = m < Mrows;
             int base;
             if (mode == VMV_SEG_LINEAR) {
                 base = m * ld; mask[i] = inm[i] ? 1u : 0u;
@@ -344,7 +364,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     float* csum = cvec + Cfg::XG_MAXG * BN;         // folded LayerNorm: the column sums of W' (vmv.h)
     const int rv_div = p.rowvec ? p.rowvec_div : (1 << 30);
     const int g0 = m0 / rv_div;
-    const int m_last = (m0 + BM < p.M ? m0 + BM : p.M) - 1;
+    const int m_last = (m0 + BM < Mrows ? m0 + BM : Mrows) - 1;
     const int ng = m_last / rv_div - g0 + 1;
     __syncthreads();                                // ring no longer read by anyone
     for (int idx = tid; idx < ng * BN; idx += Cfg::NT) {
@@ -361,7 +381,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     }
     int gi[WM];                                     // row group (relative to g0) of this lane's row in each row tile
 #pragma unroll
-    for (int i = 0; i < WM; ++i) { const int m = mbase + 16 * i; gi[i] = ((m < p.M ? m : m_last) / rv_div - g0) * BN; }
+    for (int i = 0; i < WM; ++i) { const int m = mbase + 16 * i; gi[i] = ((m < Mrows ? m : m_last) / rv_div - g0) * BN; }
     float ln_mean[WM], ln_rstd[WM];                 // folded LayerNorm: (mean, rstd) of this lane's four rows
     if constexpr (LNF) {
 #pragma unroll
@@ -440,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             const int idx = tid + it * Cfg::NT;
             const int r = idx / U, u = idx - r * U;
             const int m = m0 + hh * Cfg::HALF_ROWS + r, n = n0o + u * 8;
-            if (m >= p.M || n >= No) continue;
+            if (m >= Mrows || n >= No) continue;
             u32x4_t v = *reinterpret_cast<const u32x4_t*>(smem + r * row_bytes + u * 16);
             if (resp) {
                 float a[8], b[8];
@@ -453,16 +473,18 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             __builtin_amdgcn_s_waitcnt(0xc07f);
             keep_alive(sd_prev);
             const u32x4_t sd = valu_copy(v);
-            *reinterpret_cast<u32x4_t*>(outp + (size_t)m * p.ldo + n) = sd;
+            size_t orow = (size_t)m;
+            if constexpr (UP4) orow = (size_t)(4 * m - 2 * (m % p.IW) + (ph >> 1) * p.OW + (ph & 1));      // (n OH + 2 i + py) OW + 2 j + px
+            *reinterpret_cast<u32x4_t*>(outp + orow * p.ldo + n) = sd;
             sd_prev = sd;
         }
     }
 }
 
-template <int NH, int WH, int EPI = 0, int WNV = 2>
+template <int NH, int WH, int EPI = 0, int WNV = 2, bool UP4 = false>
 int launch_xglds(const VmvGemmParams& p, hipStream_t st) {
     using Cfg = WgCfg<NH, WH, WNV>;
-    const int tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
+    const int tiles_m = UP4 ? 4 * ((p.M / 4 + Cfg::BM - 1) / Cfg::BM) : (p.M + Cfg::BM - 1) / Cfg::BM;      // (UP4: four phases of M / 4 rows)
     const int tiles_n = (p.N + Cfg::BN - 1) / Cfg::BN;
     const int gm = gemm_group_m(tiles_m, tiles_n, Cfg::BM, Cfg::BN, 32);
     int nsteps = 0;                                          // chunks of WBK = 32 (vmv_gemm counts the other kernels' 64)
@@ -470,7 +492,7 @@ int launch_xglds(const VmvGemmParams& p, hipStream_t st) {
     if (nsteps < Cfg::STAGES || (nsteps & 1)) return VMV_GLDS_UNSUPPORTED;
     if (p.rowvec && (Cfg::BM - 1) / p.rowvec_div + 2 > Cfg::XG_MAXG) return VMV_GLDS_UNSUPPORTED;      // column vectors staged per row group
     if (p.ksplit > 1) {
-        if constexpr (EPI != 0 || WNV != 2) return VMV_GLDS_UNSUPPORTED;
+        if constexpr (EPI != 0 || WNV != 2 || UP4) return VMV_GLDS_UNSUPPORTED;
         else {
             // even chunk counts per split (the loop body is two chunks), every split >= STAGES chunks, no empty split
             int sps = (nsteps + p.ksplit - 1) / p.ksplit;
@@ -485,8 +507,8 @@ int launch_xglds(const VmvGemmParams& p, hipStream_t st) {
         }
     }
     static std::atomic<unsigned long long> attr_set{0};
-    if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_xglds_kernel<NH, WH, EPI, false, WNV>), Cfg::LDS_BYTES)) return rc_attr;
-    VMV_LAUNCH((gemm_xglds_kernel<NH, WH, EPI, false, WNV>), dim3(tiles_m * tiles_n), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, nsteps, nsteps, gm, 1);
+    if (const int rc_attr = vmv_lds_attr_once(attr_set, reinterpret_cast<const void*>(&gemm_xglds_kernel<NH, WH, EPI, false, WNV, UP4>), Cfg::LDS_BYTES)) return rc_attr;
+    VMV_LAUNCH((gemm_xglds_kernel<NH, WH, EPI, false, WNV, UP4>), dim3(tiles_m * tiles_n), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, tiles_m, tiles_n, nsteps, nsteps, gm, 1);
     return vmv_launch_status();
 }
 
@@ -513,6 +535,13 @@ int vmv_gemm_xglds_launch(const VmvGemmParams& p, int total_steps, int tile, hip
     const int No = geglu ? p.N / 2 : p.N;
     if (p.ksplit <= 1 && (p.out_fp32 || (p.ldo & 7) || (No & 7) || !vmv_aligned16(p.out) ||
                           (p.residual && ((p.ldr & 7) || !vmv_aligned16(p.residual))))) return VMV_GLDS_UNSUPPORTED;   // staged epilogue only
+    if (p.phased) {      // (vmv_gemm validated the mode's contract: plain epilogue, 16-bit output, no split-K)
+        if (geglu || lnf || p.ksplit > 1 || !vmv_span32(4L * p.N + 320, p.ktot)) return VMV_GLDS_UNSUPPORTED;
+        if (tile == VMV_TILE_X256x320) return launch_xglds<2, 5, 0, 2, true>(p, st);
+        if (tile == VMV_TILE_X256x256) return launch_xglds<2, 4, 0, 2, true>(p, st);
+        if (tile == VMV_TILE_X256x128) return launch_xglds<1, 4, 0, 2, true>(p, st);
+        return VMV_GLDS_UNSUPPORTED;
+    }
     if (geglu || lnf) {
         if (geglu && lnf) return launch_xglds<2, 4, XE_GEGLU | XE_LN>(p, st);
         if (geglu) return launch_xglds<2, 4, XE_GEGLU>(p, st);

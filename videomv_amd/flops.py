@@ -5,7 +5,7 @@ from . import _lib as L
 
 
 def gemm_flops(p) -> float:
-    f = 2.0 * p.M * p.N * p.ktot
+    f = 2.0 * p.M * p.N * p.ktot       # (a phased up-convolution counts what it executes: ktot = 4 C, not the nine taps it replaces)
     if p.epilogue == L.EPI_TATTN:      # fused q | k | v + temporal attention: + QK^T and PV of every (pixel, head): 4 * F * F * 64 each
         f += 4.0 * p.M * p.F * 64 * (p.N // 192)
     return f
@@ -25,7 +25,7 @@ def gemm_bytes(p) -> float:
             rows = (p.M // (p.OH * p.OW)) * p.IH * p.IW
         b += 2.0 * rows * sg.k
     n_out = p.N // 2 if p.epilogue == L.EPI_GEGLU else (p.N // 3 if p.epilogue == L.EPI_TATTN else p.N)
-    b += 2.0 * p.N * p.ktot
+    b += 2.0 * p.N * p.ktot * (4 if p.phased else 1)
     b += (4.0 if p.out_fp32 else 2.0) * p.M * n_out
     if p.residual:
         b += 2.0 * p.M * n_out

@@ -13,6 +13,7 @@ import torch
 from . import _lib as L
 
 TAPS3x3 = [(dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+TAPS_UP4 = [(-1, -1), (-1, 0), (0, -1), (0, 0)]      # the 2 x 2 window of a phased nearest-x2 convolution (vmv.h: VmvGemmParams.phased)
 GN_REC = 8      # int64 per (stat group, channel group) record of VmvGroupNormParams.totals (include/vmv.h)
 GN_NREP = 8     # replicas of every record (chunk c adds into replica c % 8)
 GN_TOT = 32 * GN_NREP * GN_REC      # int64 per stat group
@@ -41,6 +42,12 @@ def conv3x3_segs(sources: Sequence[Tuple[torch.Tensor, int, int]], shift: int = 
     return [Seg(t, ld, k, L.SEG_SPATIAL, dy + shift, dx + shift) for (dy, dx) in TAPS3x3 for (t, ld, k) in sources]
 
 
+def up4_segs(src, ld, k) -> List[Seg]:
+    """The four taps of the phased nearest-x2 + 3x3 convolution of ONE source — the K order ``pack_conv3x3_up4`` lays each phase's
+    summed weights out in."""
+    return [Seg(src, ld, k, L.SEG_SPATIAL, dy, dx) for (dy, dx) in TAPS_UP4]
+
+
 def temporal_segs(src, ld, k) -> List[Seg]:
     return [Seg(src, ld, k, L.SEG_TEMPORAL, dt, 0) for dt in (-1, 0, 1)]
 
@@ -59,7 +66,7 @@ class Geom:
 def gemm_params(M, N, segs: Sequence[Seg], W, out, ldo, bias=None, rowvec=None, rowvec_div=1, rowvec_ld=0,
                 residual=None, ldr=0, epilogue=L.EPI_NONE, act=L.ACT_NONE, out_fp32=False, geom: Optional[Geom] = None,
                 ksplit=0, workspace=None, tile=L.TILE_AUTO, res_scale=0.0, rowstat=None, colsum=None, ln_eps=0.0, wgroup_rows=0, wgroup_stride=0,
-                gn_table=None, gn_rows_per_stat=0, gn_silu=False, epi_scale=0.0) -> L.GemmParams:
+                gn_table=None, gn_rows_per_stat=0, gn_silu=False, epi_scale=0.0, phased=False) -> L.GemmParams:
     p = L.GemmParams()
     p.M, p.N, p.nseg = int(M), int(N), len(segs)
     if len(segs) > L.VMV_MAX_SEGS:
@@ -82,6 +89,7 @@ def gemm_params(M, N, segs: Sequence[Seg], W, out, ldo, bias=None, rowvec=None, 
     p.wgroup_rows, p.wgroup_stride = int(wgroup_rows), int(wgroup_stride)
     p.gn_table, p.gn_rows_per_stat = _ptr(gn_table), int(gn_rows_per_stat)       # GroupNorm folded into the A rows (vmv.h; gemm_rs / gemm_tfr)
     p.gn_silu = 1 if gn_silu else 0
+    p.phased = 1 if phased else 0                         # nearest-x2 + 3x3 as four 2x2 phase convolutions (W = [4][N][ktot])
     p.epi_scale = float(epi_scale)                         # VMV_EPI_TATTN: softmax scale of the fused temporal attention (gemm_tqa.hip)
     return p
 
@@ -120,7 +128,7 @@ def gemm_signature(p: "L.GemmParams") -> str:
         i = j
     flags = (f"e{p.epilogue}a{p.act}f{p.out_fp32}r{int(bool(p.residual))}v{int(bool(p.rowvec))}:{p.rowvec_div if p.rowvec else 0}"
              f"s{int(bool(p.rowstat))}c{int(bool(p.colsum))}l{int(p.ln_eps > 0)}g{int(bool(p.gn_table)) + 2 * int(bool(p.gn_silu))}w{p.wgroup_rows}")
-    geo = f"{p.OH}x{p.OW}<{p.IH}x{p.IW}s{p.stride}u{p.ups}F{p.F}P{p.P}"
+    geo = f"{p.OH}x{p.OW}<{p.IH}x{p.IW}s{p.stride}u{p.ups}{'p' if p.phased else ''}F{p.F}P{p.P}"
     return f"{p.M}x{p.N}x{p.ktot};{','.join(runs)};{flags};{geo}"
 
 
@@ -170,6 +178,8 @@ def fill_rule(p: "L.GemmParams", policy_tile: int):
       * short-K linears on a few thousand rows (200-1024 tiles of 64 x 64): 64 x 64 register tiles.
     -> (tile, ksplit) or None (keep the policy's choice).  The caller validates the choice with vmv_gemm_validate before forcing it."""
     import math
+    if p.phased:        # the phased up-convolution has its own three wide tiles (csrc/gemm.hip final_tile); measured entries only
+        return None
     M, N = p.M, p.N
     steps = sum((p.seg[i].k + 63) // 64 for i in range(p.nseg))
     geglu = p.epilogue == L.EPI_GEGLU

@@ -5,6 +5,8 @@ tensor ops (pure data movement — no arithmetic of the hot path happens here).
 K ordering rules (must match ``ops.conv3x3_segs`` / ``ops.temporal_segs``):
   * 3x3 conv  [N, C, 3, 3]     -> [N, 9*C']  tap-major (dy, dx row-major), channels within a tap;
                                   C' = C zero-padded to a multiple of 8 (only the 4-channel latent convs)
+  * nearest-x2 + 3x3 conv as four 2x2 phase convs [N, C, 3, 3] -> [4*N, 4*C'] (``pack_conv3x3_up4``: the one place where weights are
+                                  ADDED — in fp32, once per checkpoint — before the rounding to 16 bits)
   * temporal  [N, C, 3, 1, 1]  -> [N, 3*C]   taps dt = -1, 0, +1
   * linear / 1x1 / Conv1d(k=1) -> [N, K]
   * GEGLU     [2*I, K]         -> rows interleaved in 16-row blocks: x[16j:16j+16], gate[16j:16j+16]
@@ -40,6 +42,35 @@ def pack_conv3x3(w: torch.Tensor, device) -> torch.Tensor:
         w = torch.cat([w, w.new_zeros(n, padc, 3, 3)], dim=1)
     w = w.permute(0, 2, 3, 1).reshape(n, -1)
     return _pad_rows(w).to(device=device, dtype=L.elem()).contiguous()
+
+
+# kernel rows / columns of the 3x3 window that meet tap a (= d0 + 1) of output phase py: R[py][a]  (vmv.h: VmvGemmParams.phased)
+UP4_R = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def up4_sum_weights(w: torch.Tensor) -> torch.Tensor:
+    """[N, C, 3, 3] -> [4, N, 4 * C] in w's own dtype (no rounding): the summed weights of the four phase convolutions,
+        W4[2 py + px][n][(a, b), c] = sum_{ky in R[py][a]} sum_{kx in R[px][b]} w[n][c][ky][kx]        (R = UP4_R; K order = ops.up4_segs)"""
+    n = w.shape[0]
+    phases = []
+    for py in (0, 1):
+        for px in (0, 1):
+            taps = [sum(w[:, :, ky, kx] for ky in UP4_R[py][a] for kx in UP4_R[px][b]) for a in (0, 1) for b in (0, 1)]      # 4 x [n, c]
+            phases.append(torch.stack(taps, dim=1).reshape(n, -1))
+    return torch.stack(phases, dim=0)
+
+
+def pack_conv3x3_up4(w: torch.Tensor, device) -> torch.Tensor:
+    """Weights of a nearest-x2 + 3x3 convolution [N, C, 3, 3] as four 2x2 phase convolutions -> [4 * N', 4 * C'] (phase-major; N' / C' padded
+    as in ``pack_conv3x3``): summed in fp32 from the fp32 weights and rounded ONCE to the 16-bit type."""
+    n, c, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    w = w.float()
+    padc = (-c) % 8
+    if padc:
+        w = torch.cat([w, w.new_zeros(n, padc, 3, 3)], dim=1)
+    w4 = up4_sum_weights(w)
+    return torch.cat([_pad_rows(w4[ph]) for ph in range(4)], dim=0).to(device=device, dtype=L.elem()).contiguous()
 
 
 def pack_tconv(w: torch.Tensor, device) -> torch.Tensor:

@@ -401,6 +401,7 @@ class UNetEngine:
                     w[f"{p}.bias"] = P.pack_bias(sd[f"{p}.op.bias"], dev)
                 elif kind == "up":
                     w[f"{p}.weight"] = P.pack_conv3x3(sd[f"{p}.conv.weight"], dev)
+                    w[f"{p}.weight.up4"] = P.pack_conv3x3_up4(sd[f"{p}.conv.weight"], dev)      # (engines of every size share this dict)
                     w[f"{p}.bias"] = P.pack_bias(sd[f"{p}.conv.bias"], dev)
         self.emb_total = off
         w["emb_all.weight"] = P.pack_linear(torch.cat(emb_w, dim=0), dev)
@@ -452,6 +453,18 @@ class UNetEngine:
         ks, ws = (0, None) if kw.get("rowstat") else self._ksplit(M, W.shape[0], segs)      # (folded-LN GEMMs: no split-K)
         p = ops.gemm_params(M, W.shape[0], segs, W, out.ptr, out.C, bias=bias, geom=geom, ksplit=ks, workspace=ws, **kw)
         (stream or self.S).gemm(p, label)
+
+    def _up_conv(self, label, M, xin: Act, out: Act, geom):
+        """Upsample (nearest x2 -> 3x3 convolution, util.py:595-606): ONE launch — four 2x2 phase convolutions over the source pixels with
+        the pre-summed weights (K = 4 C; vmv.h VmvGemmParams.phased) where the library prefers that form (vmv_gemm_up4_ok), else the
+        nine-tap gather over the up-sampled image."""
+        W4 = self.w[label + ".weight.up4"]
+        p = ops.gemm_params(M, W4.shape[0] // 4, ops.up4_segs(xin.ptr, xin.C, xin.C), W4, out.ptr, out.C, bias=self.w[label + ".bias"],
+                            geom=geom, phased=True)
+        if self.S.lib.vmv_gemm_up4_ok(C.byref(p)):
+            self.S.gemm(p, label)
+        else:
+            self._gemm(label, M, out.C, ops.conv3x3_segs([(xin.ptr, xin.C, xin.C)]), label + ".weight", out, bias=self.w[label + ".bias"], geom=geom)
 
     def _ksplit(self, M, N, segs):
         """Split K when the tile grid cannot fill 256 CUs and the reduction is long (small-spatial levels)."""
@@ -924,8 +937,7 @@ class UNetEngine:
                 oh, ow = h * 2, w * 2
                 T = self.B * self.F * oh * ow
                 y = self.act(T, m["c"])
-                self._gemm(p, T, m["c"], ops.conv3x3_segs([(xin.ptr, xin.C, xin.C)]), p + ".weight", y,
-                           bias=self.w[p + ".bias"], geom=ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=1, ups=1))
+                self._up_conv(p, T, xin, y, ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=1, ups=1))
                 h, w = oh, ow
             else:
                 raise ValueError(kind)
