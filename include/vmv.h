@@ -235,6 +235,12 @@ int vmv_gemm_pick_tile(const VmvGemmParams* p);
  * would return otherwise.  Needs no GPU.  The Python host calls it when a measured (tile, split-K) entry of tuned_gemm.json is about
  * to be forced on a recorded launch: a stale entry is dropped there, with a warning, instead of aborting the first replay. */
 int vmv_gemm_validate(const VmvGemmParams* p);
+/* The VMV_TILE_* id of the kernel family vmv_gemm(p, stream) would finally launch, after every launcher fallback: the same dry run as
+ * vmv_gemm_validate (no launch, no device access).  A forced tile whose launcher cannot address the operands is served by another kernel
+ * (persistent and wide tiles -> VMV_TILE_256x128 / 256x160 -> the register-staged kernel, reported as VMV_TILE_128x128 / 128x160 / 128x64 /
+ * 64x64); vmv_gemm_pick_tile names the first choice, this the kernel that writes the output.  Returns the negative VMV_E* code
+ * vmv_gemm_validate would when nothing launches.  (additive: ABI 11) */
+int vmv_gemm_served_tile(const VmvGemmParams* p);
 /* The block -> tile map every GEMM kernel uses (XCD-aware bijection, grouped order for gm > 1), on the host: the (row tile, column
  * tile) block `bid` of a tiles_m x tiles_n grid works on.  VMV_EINVAL unless 0 <= bid < tiles_m * tiles_n and gm >= 1.  Needs no GPU. */
 int vmv_gemm_tile_map(int bid, int tiles_m, int tiles_n, int gm, int* tile_m, int* tile_n);

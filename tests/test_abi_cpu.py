@@ -275,6 +275,26 @@ def test_gemm_validate_is_the_launch_without_the_device():
         ops._TUNED, ops._STALE_WARNED = old, old_w
 
 
+def test_gemm_served_tile_names_the_kernel_after_the_fallbacks():
+    """vmv_gemm_served_tile: the symbol exists and answers, without a device, with the kernel family vmv_gemm would finally launch —
+    the forced tile for a dense linear it serves, the fallback for one it declines, the VMV_E* code when nothing launches."""
+    lib = L.load()
+    X = 1 << 20
+    p = ops.gemm_params(4096, 1280, ops.linear_segs([(X, 1280, 1280)]), X, X, 1280, tile=L.TILE_P256x128)
+    assert lib.vmv_gemm_served_tile(C.byref(p)) == L.TILE_P256x128
+    assert lib.vmv_gemm_validate(C.byref(p)) == 0
+    p.tile = L.TILE_128x64
+    assert lib.vmv_gemm_served_tile(C.byref(p)) == L.TILE_128x64
+    p.tile = L.TILE_AUTO
+    assert lib.vmv_gemm_served_tile(C.byref(p)) == lib.vmv_gemm_pick_tile(C.byref(p))
+    # persistent kernels take linear segments only: a forced P tile over 3 x 3 taps runs the 256 x 128 LDS-DMA kernel
+    q = ops.gemm_params(4096, 128, ops.conv3x3_segs([(X, 64, 64)]), X, X, 128, geom=ops.Geom(OH=64, OW=64, IH=64, IW=64), tile=L.TILE_P256x128)
+    assert lib.vmv_gemm_served_tile(C.byref(q)) == L.TILE_256x128
+    p.tile = L.TILE_RS                       # K = 1280: the row-stationary kernel does not exist
+    assert lib.vmv_gemm_served_tile(C.byref(p)) == -1
+    assert lib.vmv_gemm_served_tile(None) == -3
+
+
 def _tile_map_py(bid, tiles_m, tiles_n, gm):
     """The kernels' block -> tile map (gemm_common.h), written out."""
     nblk = tiles_m * tiles_n

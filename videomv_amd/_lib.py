@@ -191,6 +191,7 @@ SYMBOLS = {
     "vmv_ff_fused_ok": (C.c_int, [C.POINTER(FfParams)]),
     "vmv_gemm_pick_tile": (C.c_int, [C.POINTER(GemmParams)]),
     "vmv_gemm_validate": (C.c_int, [C.POINTER(GemmParams)]),
+    "vmv_gemm_served_tile": (C.c_int, [C.POINTER(GemmParams)]),
     "vmv_gemm_tile_map": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vmv_gemm_group_m": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vmv_groupnorm_stats": (C.c_int, [C.POINTER(GroupNormParams), _P]),

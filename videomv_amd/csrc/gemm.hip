@@ -413,6 +413,8 @@ bool up4_valid(const VmvGemmParams& p) {
 bool ln_inline_ok(const VmvGemmParams& p) {
     if (!p.W || !p.out || !p.colsum || p.nseg != 1 || p.seg[0].mode != VMV_SEG_LINEAR || p.seg[0].k != p.ktot) return false;
     if (p.ksplit > 1 || p.out_fp32 || p.rowvec || p.residual) return false;
+    // the fused q | k | v + temporal attention takes the statistics from its resident rows: its own tile id, forced or picked
+    if (p.epilogue == VMV_EPI_TATTN) return (p.tile == VMV_TILE_AUTO || p.tile == VMV_TILE_TQA) && vmv_gemm_tqa_supported(p);
     const bool rs_forced = p.tile == VMV_TILE_RS || p.tile == VMV_TILE_RS512 || p.tile == VMV_TILE_RS256;
     if (p.tile != VMV_TILE_AUTO && p.tile != VMV_TILE_P256x128 && p.tile != VMV_TILE_P256x160 && !rs_forced) return false;
     const int n_out = p.epilogue == VMV_EPI_GEGLU ? p.N / 2 : p.N;
@@ -472,6 +474,20 @@ extern "C" int vmv_gemm_validate(const VmvGemmParams* pp) {
     const int rc = vmv_gemm(pp, nullptr);
     vmv_dry_run = 0;
     return rc;
+}
+
+// vmv_gemm_served_tile: in dry-run mode every launcher call of vmv_gemm's switch notes the kernel family it reached — a launcher that
+// declines (VMV_GLDS_UNSUPPORTED) notes nothing, so after the fallbacks the note names the kernel the same call would launch.
+static thread_local int vmv_served_note = 0;
+static inline int served(int rc, int tile) {
+    if (vmv_dry_run && rc != VMV_GLDS_UNSUPPORTED) vmv_served_note = tile;
+    return rc;
+}
+extern "C" int vmv_gemm_served_tile(const VmvGemmParams* pp) {
+    vmv_served_note = 0;
+    const int rc = vmv_gemm_validate(pp);
+    if (rc != VMV_OK) return rc < 0 ? rc : VMV_EINVAL;
+    return vmv_served_note > 0 ? vmv_served_note : VMV_EINVAL;
 }
 
 // the kernels' block -> tile map and the launchers' group size, for the host-side tests (gemm_common.h)
@@ -539,93 +555,93 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
     const int picked = final_tile(p, total_steps);
     if (picked < 0) return picked;
     switch (picked) {
-        case VMV_TILE_128x128: rc = launch_cfg<4, 4>(p, total_steps, st); break;
+        case VMV_TILE_128x128: rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128); break;
         case VMV_TILE_128x160:
             if (p.epilogue == VMV_EPI_GEGLU) return VMV_EINVAL;
-            rc = launch_cfg<4, 5>(p, total_steps, st); break;
-        case VMV_TILE_128x64: rc = launch_cfg<4, 2>(p, total_steps, st); break;
-        case VMV_TILE_64x64: rc = launch_cfg<2, 2>(p, total_steps, st); break;
+            rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160); break;
+        case VMV_TILE_128x64: rc = served(launch_cfg<4, 2>(p, total_steps, st), VMV_TILE_128x64); break;
+        case VMV_TILE_64x64: rc = served(launch_cfg<2, 2>(p, total_steps, st), VMV_TILE_64x64); break;
         case VMV_TILE_256x128:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st), VMV_TILE_256x128);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             break;
         case VMV_TILE_256x160:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st), VMV_TILE_256x160);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160);
             break;
         case VMV_TILE_X256x320:
         case VMV_TILE_X256x256:
         case VMV_TILE_X256x128:
         case VMV_TILE_X512x128:
-            rc = vmv_gemm_xglds_launch(p, total_steps, picked, st);
+            rc = served(vmv_gemm_xglds_launch(p, total_steps, picked, st), picked);
             if (rc == VMV_GLDS_UNSUPPORTED && p.phased) return VMV_EINVAL;      // (no other kernel serves the phased form)
             if (rc == VMV_GLDS_UNSUPPORTED && (p.rowstat || p.epilogue == VMV_EPI_GEGLU)) {      // the fused epilogues' other home
                 if (p.tile != VMV_TILE_AUTO) return VMV_EINVAL;
-                rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x128, st);
-                if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+                rc = served(vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x128, st), VMV_TILE_P256x128);
+                if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
                 break;
             }
             if (rc == VMV_GLDS_UNSUPPORTED) {
                 if (p.tile != VMV_TILE_AUTO) return VMV_EINVAL;
-                rc = vmv_gemm_glds_launch(p, total_steps, p.N % 160 == 0 ? VMV_TILE_256x160 : VMV_TILE_256x128, st);
-                if (rc == VMV_GLDS_UNSUPPORTED) rc = p.N % 160 == 0 ? launch_cfg<4, 5>(p, total_steps, st) : launch_cfg<4, 4>(p, total_steps, st);
+                rc = served(vmv_gemm_glds_launch(p, total_steps, p.N % 160 == 0 ? VMV_TILE_256x160 : VMV_TILE_256x128, st), p.N % 160 == 0 ? VMV_TILE_256x160 : VMV_TILE_256x128);
+                if (rc == VMV_GLDS_UNSUPPORTED) rc = p.N % 160 == 0 ? served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160) : served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             }
             break;
         case VMV_TILE_TFR:
-            rc = vmv_gemm_tfr_launch(p, st);
+            rc = served(vmv_gemm_tfr_launch(p, st), VMV_TILE_TFR);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
             break;
         case VMV_TILE_TQA:
-            rc = vmv_gemm_tqa_launch(p, st);
+            rc = served(vmv_gemm_tqa_launch(p, st), VMV_TILE_TQA);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
             break;
         case VMV_TILE_HALO:
-            rc = vmv_conv_halo_launch(p, st);
+            rc = served(vmv_conv_halo_launch(p, st), VMV_TILE_HALO);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
             break;
         case VMV_TILE_RS:
         case VMV_TILE_RS512:
         case VMV_TILE_RS256:
-            rc = vmv_gemm_rs_launch(p, picked, st);
+            rc = served(vmv_gemm_rs_launch(p, picked, st), picked);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;      // (final_tile checked eligibility: a forced row tile that does not exist)
             break;
         case VMV_TILE_Q128x128:
-            rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_Q128x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+            rc = served(vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_Q128x128, st), VMV_TILE_Q128x128);
+            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st), VMV_TILE_256x128);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             break;
         case VMV_TILE_Q96x160:
-            rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_Q96x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
+            rc = served(vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_Q96x160, st), VMV_TILE_Q96x160);
+            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st), VMV_TILE_256x160);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160);
             break;
         case VMV_TILE_P256x128:
-            rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x128, st);
+            rc = served(vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x128, st), VMV_TILE_P256x128);
             if (rc == VMV_GLDS_UNSUPPORTED && ln_inline) return VMV_EINVAL;
-            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x128, st), VMV_TILE_256x128);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             break;
         case VMV_TILE_P256x160:
-            rc = vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x160, st);
+            rc = served(vmv_gemm_pglds_launch(p, total_steps, VMV_TILE_P256x160, st), VMV_TILE_P256x160);
             if (rc == VMV_GLDS_UNSUPPORTED && ln_inline) return VMV_EINVAL;
-            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
+            if (rc == VMV_GLDS_UNSUPPORTED && !p.rowstat) rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_256x160, st), VMV_TILE_256x160);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160);
             break;
         case VMV_TILE_PP256x128:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_PP256x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_PP256x128, st), VMV_TILE_PP256x128);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             break;
         case VMV_TILE_PP256x160:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_PP256x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_PP256x160, st), VMV_TILE_PP256x160);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160);
             break;
         case VMV_TILE_G128x128:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_G128x128, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 4>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_G128x128, st), VMV_TILE_G128x128);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 4>(p, total_steps, st), VMV_TILE_128x128);
             break;
         case VMV_TILE_G128x160:
-            rc = vmv_gemm_glds_launch(p, total_steps, VMV_TILE_G128x160, st);
-            if (rc == VMV_GLDS_UNSUPPORTED) rc = launch_cfg<4, 5>(p, total_steps, st);
+            rc = served(vmv_gemm_glds_launch(p, total_steps, VMV_TILE_G128x160, st), VMV_TILE_G128x160);
+            if (rc == VMV_GLDS_UNSUPPORTED) rc = served(launch_cfg<4, 5>(p, total_steps, st), VMV_TILE_128x160);
             break;
         default: return VMV_EINVAL;
     }

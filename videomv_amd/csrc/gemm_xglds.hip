@@ -409,7 +409,9 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
     // waves still hold: 30 spilled.)  Buffer loads with out-of-range offsets for the tile tails.
     constexpr int ITER = Cfg::HALF_ROWS * U / Cfg::NT;
     constexpr int RD = EPI != 0 ? 1 : (ITER < 4 ? ITER : 4);      // (the folded-LayerNorm / GEGLU instantiations never carry a residual in the
-                                                                   //  plans and have no registers to spare: one load ahead, as before)
+                                                                   //  plans and have no registers to spare: ONE slot, requested at the top of the
+                                                                   //  iteration that consumes it — no load ahead, a dependent round trip per
+                                                                   //  iteration if a plan ever passes them a residual)
     static_assert(ITER * Cfg::NT == Cfg::HALF_ROWS * U, "store loop trip count");
     const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(resp), 0, resp ? SRD_RECORDS : 0u, SRD_FLAGS);
     auto res_request = [&](const int hh, const int it) -> u32x4_t {
@@ -460,6 +462,10 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
             const int idx = tid + it * Cfg::NT;
             const int r = idx / U, u = idx - r * U;
             const int m = m0 + hh * Cfg::HALF_ROWS + r, n = n0o + u * 8;
+            // The slot the previous iteration used is refilled HERE, before the idle-lane test, not at the end of that iteration's body: in
+            // a ragged column tile of the 320-column form (U = 40) a lane's column unit moves by 8 per RD = 4 iterations, so a lane idle
+            // in one iteration may be live RD iterations on and needs that iteration's residual in the slot.
+            if (resp && it >= 1 && it - 1 + RD < ITER) rr[(it - 1) % RD] = res_request(hh, it - 1 + RD);
             if (m >= Mrows || n >= No) continue;
             u32x4_t v = *reinterpret_cast<const u32x4_t*>(smem + r * row_bytes + u * 16);
             if (resp) {
@@ -468,7 +474,6 @@ __global__ __launch_bounds__(512, 1) void gemm_xglds_kernel(const VmvGemmParams 
 #pragma unroll
                 for (int e = 0; e < 8; ++e) a[e] += rs * b[e];
                 v = pack8(a);
-                if (it + RD < ITER) rr[it % RD] = res_request(hh, it + RD);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             keep_alive(sd_prev);
