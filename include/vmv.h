@@ -30,7 +30,7 @@ extern "C" {
 #define VMV_ERANGE       -4   /* size outside what the kernel supports */
 #define VMV_ECOMM        -5   /* an RCCL call of vmv_comm_* failed */
 
-#define VMV_ABI_VERSION   11
+#define VMV_ABI_VERSION   12
 int vmv_abi_version(void);
 /* The 16-bit storage / MFMA operand type ("elem") this build of the library computes in.  The same sources are
  * compiled once per type: libvmv_hip_f16.so (VMV_ELEM_F16: IEEE fp16 — the default; the reference's own half mode,
@@ -383,6 +383,18 @@ typedef struct {
     int32_t causal;        /* != 0: scores of keys j > query i are masked out (requires Nq == Nk, head_dim 64)         */
 } VmvAttnParams;
 int vmv_attention(const VmvAttnParams* p, void* stream);
+/* The kernels vmv_attention chooses between, by shape alone (head_dim 64 unless said): */
+#define VMV_ATTN_SHORT    1   /* Nq <= 32 and Nk <= 32: one wave per problem, every load issued up front (the 24-frame temporal attention) */
+#define VMV_ATTN_WAVE     2   /* Nq <= 32 < Nk: one wave per problem, key tiles of 64 (cross-attention of the smallest levels)           */
+#define VMV_ATTN_Q128     3   /* the general case: four waves share a 128-query block                                                    */
+#define VMV_ATTN_Q256     4   /* 256-query blocks: Nk >= 512, >= 512 such blocks, Nq % 256 == 0 or Nq >= 2048                            */
+#define VMV_ATTN_CAUSAL   5   /* causal != 0 (Nq == Nk)                                                                                  */
+#define VMV_ATTN_D32      6   /* head_dim 32                                                                                             */
+#define VMV_ATTN_D128     7   /* head_dim 128                                                                                            */
+/* The VMV_ATTN_* id of the kernel vmv_attention(p, stream) would launch, or the negative VMV_E* code it would return instead: the
+ * same host function decides for both (every argument check, then the shape thresholds), so they cannot disagree.  No launch, no
+ * device access; needs no GPU.  (additive: ABI 12) */
+int vmv_attention_served_kernel(const VmvAttnParams* p);
 
 /* ------------------------------------------------------------------------------------------------------
  * Sampler glue kernels (DiffusionDDIM.p_mean_variance / ddim_sample: diffusion_ddim.py:157-160,192-195,233-243;

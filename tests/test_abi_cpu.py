@@ -21,7 +21,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert declared == set(L.SYMBOLS), declared ^ set(L.SYMBOLS)
-    assert lib.vmv_abi_version() == L.ABI_VERSION == 11
+    assert lib.vmv_abi_version() == L.ABI_VERSION == 12
 
 
 def test_struct_layouts_match_c():
@@ -293,6 +293,25 @@ def test_gemm_served_tile_names_the_kernel_after_the_fallbacks():
     p.tile = L.TILE_RS                       # K = 1280: the row-stationary kernel does not exist
     assert lib.vmv_gemm_served_tile(C.byref(p)) == -1
     assert lib.vmv_gemm_served_tile(None) == -3
+
+
+def test_attention_served_kernel_names_the_kernel_without_a_device():
+    """vmv_attention_served_kernel: the symbol exists and answers, without a device, with the VMV_ATTN_* id of the kernel vmv_attention
+    would launch, or with the VMV_E* code it would return (the full table and the rejections: tests/test_attention_cpu.py)."""
+    lib = L.load()
+    X = 1 << 20
+
+    def shape(n_outer, heads, Nq, Nk, **kw):
+        Cc = heads * kw.get("head_dim", 64)
+        m, km = ops.seq_map(Nq * Cc, 0, Cc), ops.seq_map(Nk * 2 * Cc, 0, 2 * Cc)
+        return ops.attn_params(X, X, X + 2 * Cc, X, m, km, km, m, n_outer, heads, Nq, Nk, 0.125, **kw)
+    for args, kw, want in (((5120, 5, 24, 24), {}, L.ATTN_SHORT), ((48, 20, 16, 77), dict(kv_div=24), L.ATTN_WAVE), ((48, 10, 640, 640), {}, L.ATTN_Q128),
+                           ((48, 5, 2560, 2560), {}, L.ATTN_Q256), ((2, 16, 77, 77), dict(causal=True), L.ATTN_CAUSAL),
+                           ((1, 16, 4096, 4096), dict(head_dim=32), L.ATTN_D32), ((2, 16, 257, 257), dict(head_dim=128), L.ATTN_D128)):
+        assert lib.vmv_attention_served_kernel(C.byref(shape(*args, **kw))) == want, (args, kw)
+    p = shape(48, 5, 2560, 2560, head_dim=48)
+    assert lib.vmv_attention_served_kernel(C.byref(p)) == lib.vmv_attention(C.byref(p), None) == -1
+    assert lib.vmv_attention_served_kernel(None) == -3
 
 
 def _tile_map_py(bid, tiles_m, tiles_n, gm):

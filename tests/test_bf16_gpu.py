@@ -1,7 +1,7 @@
 """Hardware parity evidence for the OTHER 16-bit element type: a process loads ONE of the two libraries, so
 the parity subset — reference golden, per-block taps against the oracle, the fused CFG + DDIM loop, the GEMM / attention /
-row-stationary kernel tests — is run once more in a child process with VMV_DTYPE=bf16 (the tests switch to the bf16 tolerances of
-DESIGN.md §6 by the loaded library: 3e-2 / 3e-2 / 6e-2; bf16 is the range fallback, fp16 the default)."""
+row-stationary kernel tests, the whole attention matrix of tests/test_attention_gpu.py (every test there is a test_attention*) — is
+run once more in a child process with VMV_DTYPE=bf16 (the tests switch to the bf16 tolerances of DESIGN.md §6 by the loaded library: 3e-2 / 3e-2 / 6e-2; bf16 is the range fallback, fp16 the default)."""
 import os
 import subprocess
 import sys
@@ -23,7 +23,7 @@ def test_other_element_type_parity_in_child_process():
     from videomv_amd import _lib as L
     other = "bf16" if L.elem_name() == "fp16" else "fp16"
     env = dict(os.environ, VMV_DTYPE=other, VMV_DTYPE_CHILD="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_unet_gpu.py", "tests/test_kernels_gpu.py", "-q", "-x", "-m", "gpu",
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_unet_gpu.py", "tests/test_kernels_gpu.py", "tests/test_attention_gpu.py", "-q", "-x", "-m", "gpu",
                         "-p", "no:cacheprovider", "-k", SUBSET], cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
     tail = r.stdout[-4000:] + r.stderr[-2000:]
     assert r.returncode == 0, tail

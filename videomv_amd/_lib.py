@@ -53,7 +53,8 @@ TILE_X256x320, TILE_X256x256, TILE_X256x128 = 20, 21, 22
 TILE_RS, TILE_RS512, TILE_RS256, TILE_HALO, TILE_TFR, TILE_TQA, TILE_W256x256, TILE_X512x128, TILE_Y256x128 = 23, 24, 25, 26, 27, 28, 29, 30, 31
 OP_GEMM, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTENTION, OP_SOFTMAX, OP_COPY, OP_GN_FUSED, OP_FF, OP_GN_TABLE, OP_COMM = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 COMM_ALL_TO_ALL, COMM_ALL_GATHER, COMM_ID_BYTES = 0, 1, 128
-ABI_VERSION = 11
+ABI_VERSION = 12
+ATTN_SHORT, ATTN_WAVE, ATTN_Q128, ATTN_Q256, ATTN_CAUSAL, ATTN_D32, ATTN_D128 = 1, 2, 3, 4, 5, 6, 7
 GN_FUSED_BYTES = 131072
 
 
@@ -200,6 +201,7 @@ SYMBOLS = {
     "vmv_groupnorm_fused": (C.c_int, [C.POINTER(GroupNormParams), C.c_int32, _P]),
     "vmv_layernorm": (C.c_int, [C.POINTER(LayerNormParams), _P]),
     "vmv_attention": (C.c_int, [C.POINTER(AttnParams), _P]),
+    "vmv_attention_served_kernel": (C.c_int, [C.POINTER(AttnParams)]),
     "vmv_softmax_rows": (C.c_int, [C.POINTER(SoftmaxParams), _P]),
     "vmv_permute_copy": (C.c_int, [C.POINTER(CopyParams), _P]),
     "vmv_gaussian_activation": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),

@@ -517,9 +517,10 @@ int map_ok(const VmvSeqMap& m) {
     return m.inner > 0 && !(m.s_outer & 7) && !(m.s_inner & 7) && !(m.s_row & 3);
 }
 
-}  // namespace
-
-extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
+// The ONE host decision of this file: every argument check of vmv_attention and the choice between its seven kernels.  Returns the
+// VMV_ATTN_* id of the kernel to launch, or the negative VMV_E* code; touches no device.  vmv_attention switches on the result and
+// vmv_attention_served_kernel returns it, so the two cannot disagree.
+int attn_decide(const VmvAttnParams* pp) {
     if (!pp) return VMV_ENULL;
     const VmvAttnParams& p = *pp;
     if (!p.q || !p.k || !p.v || !p.o) return VMV_ENULL;
@@ -536,41 +537,66 @@ extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
     if (!map_ok(p.qm) || !map_ok(p.km) || !map_ok(p.vm) || !map_ok(p.om)) return VMV_EALIGN;
     if ((p.qm.s_row & 7) || (p.km.s_row & 7) || (p.vm.s_row & 7)) return VMV_EALIGN;
     if (!vmv_aligned16(p.q) || !vmv_aligned16(p.k) || !vmv_aligned16(p.v) || (((uintptr_t)p.o) & 7)) return VMV_EALIGN;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int hd = p.head_dim ? p.head_dim : 64;
     if (p.causal && (hd != 64 || p.Nq != p.Nk)) return VMV_EINVAL;          // causal: self-attention on the general head_dim-64 kernel
-    if (hd == 32) {                  // LGM MVAttention (core/attention.py:67-84): long sequences only
-        if (p.n_outer > 65535 || p.heads > 65535) return VMV_ERANGE;
-        hipLaunchKernelGGL((attn_kernel<4, 2, 32>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
-        return vmv_launch_status();
-    }
-    if (hd == 128) {                 // zero-padded wide heads (the CLIP image tower's head_dim 80 packed to 128: clip_vision.py)
-        if (p.n_outer > 65535 || p.heads > 65535) return VMV_ERANGE;
+    const bool grid3 = p.n_outer <= 65535 && p.heads <= 65535;              // (query tile, head, problem) grid of the 4-waves-per-problem kernels
+    if (hd == 32) return grid3 ? VMV_ATTN_D32 : VMV_ERANGE;                 // LGM MVAttention (core/attention.py:67-84): long sequences only
+    if (hd == 128) return grid3 ? VMV_ATTN_D128 : VMV_ERANGE;               // zero-padded wide heads (the CLIP image tower's head_dim 80 packed to 128: clip_vision.py)
+    if (hd != 64) return VMV_EINVAL;
+    if (p.Nq <= 32 && p.Nk <= 32 && !p.causal) return VMV_ATTN_SHORT;
+    if (p.Nq <= 32 && !p.causal) return VMV_ATTN_WAVE;
+    if (!grid3) return VMV_ERANGE;
+    if (p.causal) return VMV_ATTN_CAUSAL;
+    // (round 6: 64-query blocks — QT = 1, 84 registers, four blocks per CU — for the short problems (Nk <= 192 or Nq <= 192: cross-
+    //  attention, third-level / middle self-attention) measured step-neutral: 47.88 / 47.91 vs 47.86 / 47.87 ms, attention family
+    //  4.16 / 4.13 vs 4.17 / 4.17 ms, profiles/r6_attn_q64_step_ab.log — not kept)
+    // 256-query blocks when that still leaves >= 2 blocks per CU and the key loop is long enough to matter
+    const long blocks256 = (long)((p.Nq + 255) / 256) * p.heads * p.n_outer;
+    const bool big = p.Nk >= 512 && blocks256 >= 512 && (p.Nq % 256 == 0 || p.Nq >= 2048);
+    return big ? VMV_ATTN_Q256 : VMV_ATTN_Q128;
+}
+
+}  // namespace
+
+extern "C" int vmv_attention_served_kernel(const VmvAttnParams* pp) { return attn_decide(pp); }
+
+extern "C" int vmv_attention(const VmvAttnParams* pp, void* stream) {
+    const int which = attn_decide(pp);
+    if (which < 0) return which;
+    const VmvAttnParams& p = *pp;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nproblems = (which == VMV_ATTN_SHORT || which == VMV_ATTN_WAVE) ? p.n_outer * p.heads : 0;      // one wave per problem
+    const dim3 g128((p.Nq + 127) / 128, p.heads, p.n_outer), g256((p.Nq + 255) / 256, p.heads, p.n_outer);
+    switch (which) {
+    case VMV_ATTN_D32:
+        hipLaunchKernelGGL((attn_kernel<4, 2, 32>), g128, dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        break;
+    case VMV_ATTN_D128: {
         static std::atomic<unsigned long long> attr128{0};
         if (const int rc_attr = vmv_lds_attr_once(attr128, reinterpret_cast<const void*>(&attn_kernel<4, 2, 128>), 65536)) return rc_attr;
-        hipLaunchKernelGGL((attn_kernel<4, 2, 128>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), 65536, st, p, 0);
-        return vmv_launch_status();
+        hipLaunchKernelGGL((attn_kernel<4, 2, 128>), g128, dim3(256), 65536, st, p, 0);
+        break;
     }
-    if (hd != 64) return VMV_EINVAL;
-    if (p.Nq <= 32 && p.Nk <= 32 && !p.causal) {
-        const int nproblems = p.n_outer * p.heads;
+    case VMV_ATTN_SHORT:
         hipLaunchKernelGGL(attn_short_kernel, dim3((nproblems + 3) / 4), dim3(256), 0, st, p, nproblems);
-    } else if (p.Nq <= 32 && !p.causal) {
-        const int nproblems = p.n_outer * p.heads;
+        break;
+    case VMV_ATTN_WAVE: {
         static std::atomic<unsigned long long> attr1{0};
         if (const int rc_attr = vmv_lds_attr_once(attr1, reinterpret_cast<const void*>(&attn_kernel<1, 2>), 32768)) return rc_attr;
         hipLaunchKernelGGL((attn_kernel<1, 2>), dim3((nproblems + 3) / 4), dim3(256), 32768, st, p, nproblems);
-    } else {
-        if (p.n_outer > 65535 || p.heads > 65535) return VMV_ERANGE;
-        // (round 6: 64-query blocks — QT = 1, 84 registers, four blocks per CU — for the short problems (Nk <= 192 or Nq <= 192: cross-
-        //  attention, third-level / middle self-attention) measured step-neutral: 47.88 / 47.91 vs 47.86 / 47.87 ms, attention family
-        //  4.16 / 4.13 vs 4.17 / 4.17 ms, profiles/r6_attn_q64_step_ab.log — not kept)
-        // 256-query blocks when that still leaves >= 2 blocks per CU and the key loop is long enough to matter
-        const long blocks256 = (long)((p.Nq + 255) / 256) * p.heads * p.n_outer;
-        const bool big = p.Nk >= 512 && blocks256 >= 512 && (p.Nq % 256 == 0 || p.Nq >= 2048);
-        if (p.causal) hipLaunchKernelGGL((attn_kernel<4, 2, 64, true>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
-        else if (big) hipLaunchKernelGGL((attn_kernel<4, 4>), dim3((p.Nq + 255) / 256, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
-        else hipLaunchKernelGGL((attn_kernel<4, 2>), dim3((p.Nq + 127) / 128, p.heads, p.n_outer), dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        break;
+    }
+    case VMV_ATTN_CAUSAL:
+        hipLaunchKernelGGL((attn_kernel<4, 2, 64, true>), g128, dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        break;
+    case VMV_ATTN_Q256:
+        hipLaunchKernelGGL((attn_kernel<4, 4>), g256, dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        break;
+    case VMV_ATTN_Q128:
+        hipLaunchKernelGGL((attn_kernel<4, 2>), g128, dim3(256), ATTN_STAGES * 16384, st, p, 0);
+        break;
+    default:
+        return VMV_EINVAL;
     }
     return vmv_launch_status();
 }
