@@ -143,7 +143,8 @@ typedef struct {
      * path — gn_table = [samples][2][C] with C = the segment width (not ktot), gn_rows_per_stat = F * P (one stat group per sample) —
      * and gn_silu != 0 applies SiLU after the affine: the GEMM multiplies elem(silu(x * scale + shift)), the values
      * vmv_groupnorm_apply(silu = 1) would have stored, with the zero padding of frames -1 / F applied AFTER the norm (as Conv3d pads
-     * the normalised tensor).  Ask vmv_gemm_tfr_ok() first.  gn_silu is ignored by the row-stationary kernel (must be 0 there).    */
+     * the normalised tensor).  Ask vmv_gemm_tfr_ok() / vmv_gemm_trs_ok() first: the same contract is served at C = 320 by the row-stationary
+     * temporal kernel (VMV_TILE_TRS, at most 8 samples).  gn_silu is ignored by the row-stationary linear kernel (must be 0 there).      */
     int32_t gn_silu;
     /* VMV_EPI_TATTN: the softmax scale (1 / sqrt(head_dim) = 0.125); ignored by every other epilogue.  (ABI 10) */
     float epi_scale;
@@ -212,6 +213,11 @@ typedef struct {
                                   epilogue, no split-K */
 #define VMV_TILE_Y256x128 31   /* retired: gemm_xglds.hip in 256-thread blocks, TWO blocks per CU: 0.62-0.92 x of the one-block forms */
 
+#define VMV_TILE_TRS      32   /* row-stationary temporal convolution at C = 320 (gemm_trs.hip): a wave keeps all F frames (F = 12, 16, 24) of 48 / F pixels
+                                  x K = 320 in registers, frame-major, applies the folded GroupNorm (+ SiLU; gn_table / gn_silu, <= 8 samples) there, W
+                                  streams tap by tap through the LDS ring and the three taps meet as a frame shift of the outputs; N % 32 == 0,
+                                  N <= 1280, optional residual */
+
 int vmv_gemm(const VmvGemmParams* p, void* stream);
 /* 1 if the host should record ONE VMV_EPI_TATTN launch for *p (a fused q | k | v + temporal-attention GEMM, epilogue already set)
  * instead of the q | k | v GEMM + vmv_attention pair: the fused kernel supports the shape and its grid fills the chip */
@@ -227,6 +233,14 @@ int vmv_gemm_rs_ok(const VmvGemmParams* p);
 /* 1 if vmv_gemm would run *p (tile = VMV_TILE_AUTO, a temporal convolution, with or without gn_table) on the frame-resident kernel
  * (VMV_TILE_TFR): the host then records statistics + vmv_groupnorm_table + this GEMM instead of statistics + apply + GEMM */
 int vmv_gemm_tfr_ok(const VmvGemmParams* p);
+/* 1 if vmv_gemm would run *p (tile = VMV_TILE_AUTO) on the row-stationary temporal kernel (VMV_TILE_TRS): a C = 320 temporal convolution
+ * in the folded form (gn_table set), F = 12 / 16 / 24, that the frame-resident kernel's policy does not take, with at least
+ * VMV_TRS_MIN_ITEMS (environment, default 128) items of (128 / F-pixel row tile, 64-channel group).  The host then records statistics +
+ * vmv_groupnorm_table + this GEMM, as for vmv_gemm_tfr_ok.  A forced tile = VMV_TILE_TRS also runs the unfolded form. */
+int vmv_gemm_trs_ok(const VmvGemmParams* p);
+/* vmv_gemm(p, stream) for p->tile == VMV_TILE_TRS with the kernel's persistent grid capped at max_blocks >= 1 (tests and tools: item
+ * ranges that cross row tiles at small shapes) */
+int vmv_gemm_trs_blocks(const VmvGemmParams* p, int max_blocks, void* stream);
 /* the VMV_TILE_* configuration vmv_gemm's policy picks for *p when p->tile == VMV_TILE_AUTO (p->tile otherwise); host logic only:
  * no launch, no device access (a launcher may still fall back when it cannot address the operands) */
 int vmv_gemm_pick_tile(const VmvGemmParams* p);

@@ -110,6 +110,37 @@ def main():
             ms = bench(lambda: S.gemm(p))
             line += f" t{tile}:{2.0 * M * N * K / ms / 1e9:7.1f}" + (f" ({1000.0 * ms:6.1f} us)" if kind in ("up9", "up4") else "")
         print(line, flush=True)
+    if not flt or "tcnv+gn" in flt:
+        tconv_norm_forms(S, dev)
+
+
+def tconv_norm_forms(S, dev):
+    """GroupNorm apply (+ SiLU) + the first level's temporal convolution, per launch sequence (the statistics pass is common to all
+    three and left out): the 256 x 320 tile behind vmv_groupnorm_apply, the row-stationary kernel (csrc/gemm_trs.hip) behind the same
+    apply pass, and the row-stationary kernel with the norm folded behind the one-block vmv_groupnorm_table launch."""
+    C = N = 320
+    for B, res in ((2, False), (2, True), (1, False), (1, True)):
+        F_, Pp = 24, 40 * 64
+        M, rps = B * F_ * Pp, F_ * Pp
+        x = (torch.randn(M, C, device=dev) * 1.5 + 0.7).to(BF)
+        y, out = torch.empty(M, C, device=dev, dtype=BF), torch.empty(M, N, device=dev, dtype=BF)
+        w = (torch.randn(N, 3 * C, device=dev) * (3 * C) ** -0.5).to(BF)
+        b, gamma, beta = torch.randn(N, device=dev), torch.ones(C, device=dev), torch.zeros(C, device=dev)
+        tab, ws = torch.zeros(B * 2 * C, device=dev), torch.zeros(ops.gn_partial_floats(M, rps, C), device=dev)
+        kw = dict(residual=torch.randn(M, N, device=dev).to(BF), ldr=N) if res else {}
+        gnp = lambda yy, silu=False: ops.gn_params(x, C, C, M, rps, ws, gamma, beta, 1e-5, silu, yy, C)
+        S.groupnorm_stats(gnp(tab)); S.groupnorm_table(gnp(tab))
+        mk = lambda src, tile, **k2: ops.gemm_params(M, N, ops.temporal_segs(src, C, C), w, out, N, bias=b, geom=ops.Geom(F=F_, P=Pp), tile=tile, **kw, **k2)
+        p_tile, p_plain = mk(y, L.TILE_X256x320), mk(y, L.TRS_TILE)
+        p_fold = mk(x, L.TRS_TILE, gn_table=tab, gn_rows_per_stat=rps, gn_silu=True)
+        g_apply, g_tab = gnp(y, True), gnp(tab)
+        forms = (("tile + apply", lambda: (S.groupnorm_apply(g_apply), S.gemm(p_tile))), ("trs plain + apply", lambda: (S.groupnorm_apply(g_apply), S.gemm(p_plain))),
+                 ("trs folded + table", lambda: (S.groupnorm_table(g_tab), S.gemm(p_fold))), ("apply alone", lambda: S.groupnorm_apply(g_apply)),
+                 ("tile alone", lambda: S.gemm(p_tile)), ("trs plain alone", lambda: S.gemm(p_plain)), ("trs folded alone", lambda: S.gemm(p_fold)))
+        line = f"tcnv+gn L0 M{M}{' +res' if res else ''}:"
+        for name, fn in forms:
+            line += f"  {name} {1000.0 * bench(fn, reps=30):6.1f} us"
+        print(line, flush=True)
 
 
 if __name__ == "__main__":

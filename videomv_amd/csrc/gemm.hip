@@ -34,6 +34,9 @@ bool vmv_gemm_tfr_preferred(const VmvGemmParams& p);
 int vmv_gemm_tqa_launch(const VmvGemmParams& p, hipStream_t st);                              // gemm_tqa.hip
 bool vmv_gemm_tqa_supported(const VmvGemmParams& p);
 bool vmv_gemm_tqa_preferred(const VmvGemmParams& p);
+int vmv_gemm_trs_launch(const VmvGemmParams& p, int max_blocks, hipStream_t st);              // gemm_trs.hip
+bool vmv_gemm_trs_supported(const VmvGemmParams& p);
+bool vmv_gemm_trs_preferred(const VmvGemmParams& p);
 namespace {
 
 template <int WM, int WN>
@@ -266,6 +269,9 @@ int pick_tile(const VmvGemmParams& p, int total_steps) {
     // temporal convolutions whose frame-resident tiles fill the chip (gemm_tfr.hip); a GroupNorm folded into a temporal convolution
     // lives in that kernel only
     if (vmv_gemm_tfr_preferred(p)) return VMV_TILE_TFR;
+    // the FOLDED C = 320 temporal convolution whose (row tile, channel group) items fill the chip: rows resident in registers, the norm
+    // applied there, the taps as a frame shift of the outputs (gemm_trs.hip)
+    if (vmv_gemm_trs_preferred(p)) return VMV_TILE_TRS;
     if (p.gn_table && p.nseg == 3 && p.seg[0].mode == VMV_SEG_TEMPORAL) return VMV_TILE_TFR;
     if (p.gn_table) return VMV_TILE_RS;             // a folded GroupNorm lives in that kernel's prologue only (vmv_gemm checks eligibility)
     // The wide-tile kernel (gemm_xglds.hip: 256 x 320 tiles, 64 x 160 wave tiles, four-stage ring of 32-deep chunks) takes the long-K
@@ -370,6 +376,7 @@ int final_tile(const VmvGemmParams& p, int total_steps) {
     }
     if (picked == VMV_TILE_HALO) return vmv_conv_halo_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TFR) return vmv_gemm_tfr_supported(p) ? picked : VMV_EINVAL;
+    if (picked == VMV_TILE_TRS) return vmv_gemm_trs_supported(p) ? picked : VMV_EINVAL;
     if (picked == VMV_TILE_TQA) return vmv_gemm_tqa_supported(p) && (p.tile == VMV_TILE_AUTO || p.tile == VMV_TILE_TQA) ? picked : VMV_EINVAL;
     const bool rs_tile = picked == VMV_TILE_RS || picked == VMV_TILE_RS512 || picked == VMV_TILE_RS256;
     if (rs_tile) return vmv_gemm_rs_supported(p) ? picked : VMV_EINVAL;      // (handles rowstat / colsum / grouped weights itself)
@@ -439,6 +446,11 @@ extern "C" int vmv_gemm_tfr_ok(const VmvGemmParams* pp) {
     return vmv_gemm_tfr_preferred(*pp) ? 1 : 0;
 }
 
+extern "C" int vmv_gemm_trs_ok(const VmvGemmParams* pp) {
+    if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
+    return vmv_gemm_trs_preferred(*pp) && vmv_gemm_validate(pp) == VMV_OK ? 1 : 0;
+}
+
 extern "C" int vmv_gemm_tqa_ok(const VmvGemmParams* pp) {
     if (!pp || pp->tile != VMV_TILE_AUTO || pp->nseg <= 0 || pp->nseg > VMV_MAX_SEGS) return 0;
     return vmv_gemm_tqa_preferred(*pp) ? 1 : 0;
@@ -488,6 +500,14 @@ extern "C" int vmv_gemm_served_tile(const VmvGemmParams* pp) {
     const int rc = vmv_gemm_validate(pp);
     if (rc != VMV_OK) return rc < 0 ? rc : VMV_EINVAL;
     return vmv_served_note > 0 ? vmv_served_note : VMV_EINVAL;
+}
+
+// vmv_gemm(p) for a forced VMV_TILE_TRS with the persistent grid capped at max_blocks (tests: item ranges that cross row tiles at small shapes)
+extern "C" int vmv_gemm_trs_blocks(const VmvGemmParams* pp, int max_blocks, void* stream) {
+    if (!pp || pp->tile != VMV_TILE_TRS || max_blocks < 1) return VMV_EINVAL;
+    if (const int rc = vmv_gemm_validate(pp)) return rc;
+    const int rc = vmv_gemm_trs_launch(*pp, max_blocks, reinterpret_cast<hipStream_t>(stream));
+    return rc == VMV_GLDS_UNSUPPORTED ? VMV_EINVAL : rc;
 }
 
 // the kernels' block -> tile map and the launchers' group size, for the host-side tests (gemm_common.h)
@@ -545,8 +565,8 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
         const long groups = ((long)p.M + p.wgroup_rows - 1) / p.wgroup_rows;
         if (!vmv_span32(1, (groups - 1) * p.wgroup_stride + (long)p.N * p.ktot)) return VMV_ERANGE;
     }
-    if (p.gn_table && !vmv_gemm_rs_supported(p) && !vmv_gemm_tfr_supported(p)) return VMV_EINVAL;      // folded GroupNorm: gemm_rs / gemm_tfr only
-    if (p.gn_silu && !(p.gn_table && vmv_gemm_tfr_supported(p))) return VMV_EINVAL;
+    if (p.gn_table && !vmv_gemm_rs_supported(p) && !vmv_gemm_tfr_supported(p) && !vmv_gemm_trs_supported(p)) return VMV_EINVAL;      // folded GroupNorm: gemm_rs / gemm_tfr / gemm_trs only
+    if (p.gn_silu && !(p.gn_table && (vmv_gemm_tfr_supported(p) || vmv_gemm_trs_supported(p)))) return VMV_EINVAL;
     const bool ln_inline = vmv_gemm_ln_inline(p);
     if (ln_inline) {       // statistics in the main loop: the persistent one-block-per-CU kernel, staged 16-bit output
         if (!ln_inline_ok(p)) return VMV_EINVAL;
@@ -589,6 +609,10 @@ extern "C" int vmv_gemm(const VmvGemmParams* pp, void* stream) {
             break;
         case VMV_TILE_TFR:
             rc = served(vmv_gemm_tfr_launch(p, st), VMV_TILE_TFR);
+            if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
+            break;
+        case VMV_TILE_TRS:
+            rc = served(vmv_gemm_trs_launch(p, 0, st), VMV_TILE_TRS);
             if (rc == VMV_GLDS_UNSUPPORTED) return VMV_EINVAL;
             break;
         case VMV_TILE_TQA:

@@ -542,18 +542,26 @@ class UNetEngine:
 
     def _tconv_folded(self, q, cur: Act, T, rps, out: Act, tg, residual=None, ldr=0) -> bool:
         """One step of TemporalConvBlock_v2 (util.py:1357-1392: GroupNorm over all frames -> SiLU -> Conv3d (3,1,1)) with the norm's
-        apply pass folded into the convolution: statistics (integer totals, as _gn) + a one-block table launch + the frame-resident
-        kernel (csrc/gemm_tfr.hip), which applies elem(silu(x * scale + shift)) to its A tile on the way through LDS — the values
-        vmv_groupnorm_apply would have stored.  The normalised tensor is never written or re-read.  Taken where the library's policy
-        runs the convolution on that kernel (vmv_gemm_tfr_ok: its tiles fill the chip — the first level at 24 x 40 x 64 and
-        24 x 32 x 32); frame-parallel plans gather their totals between the statistics and the table launch as before."""
+        apply pass folded into the convolution: statistics (integer totals, as _gn) + a one-block table launch + a kernel that applies
+        elem(silu(x * scale + shift)) — the values vmv_groupnorm_apply would have stored — to the rows it multiplies: the
+        row-stationary kernel (csrc/gemm_trs.hip, on its resident rows in registers) or the frame-resident kernel (csrc/gemm_tfr.hip,
+        on its A tile in LDS).  The normalised tensor is never written or re-read.  Taken where the library's policy runs the folded
+        convolution on one of them (vmv_gemm_trs_ok: C = 320 with enough items to fill the chip — the first level at 24 x 40 x 64;
+        vmv_gemm_tfr_ok: its tiles fill whole rounds — the first level at 24 x 32 x 32); frame-parallel plans gather their totals
+        between the statistics and the table launch as before."""
         Cc = cur.C
         nstat = T // rps
         W = self.w[f"{q}.weight"]
         tab = self.act(nstat * 2, Cc, dtype=torch.float32)
         gp = ops.gemm_params(T, W.shape[0], ops.temporal_segs(cur.ptr, Cc, Cc), W, out.ptr, out.C, bias=self.w[f"{q}.bias"], geom=tg,
                              residual=residual, ldr=ldr, gn_table=tab.ptr, gn_rows_per_stat=rps, gn_silu=True)
-        if not self.S.lib.vmv_gemm_tfr_ok(C.byref(gp)):
+        trs = bool(self.S.lib.vmv_gemm_trs_ok(C.byref(gp)))
+        if trs:         # a MEASURED kernel choice for the two-launch form of this very launch (tuned_gemm.json) stands: the fold has no
+            #             measurement against it (the smaller grids: 24 x 32 x 32's shared prefix, the frame-parallel ranks)
+            plain = ops.gemm_params(T, W.shape[0], ops.temporal_segs(cur.ptr, Cc, Cc), W, out.ptr, out.C, bias=self.w[f"{q}.bias"], geom=tg,
+                                    residual=residual, ldr=ldr)
+            trs = ops.gemm_signature(plain) not in ops.tuned_table()
+        if not (trs or self.S.lib.vmv_gemm_tfr_ok(C.byref(gp))):
             self.release(tab)
             return False
         label = q + ".gn"
