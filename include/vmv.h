@@ -44,7 +44,8 @@ int vmv_elem_type(void);
 int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
- * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams, 107 = VmvGsSsimLossParams */
+ * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams, 107 = VmvGsSsimLossParams,
+ * 108 = VmvGsDepthParams */
 int vmv_sizeof(int which);
 /* human-readable text for a code returned by any launcher (VMV_E* or hipError_t) */
 const char* vmv_error_string(int code);
@@ -569,6 +570,22 @@ int vmv_gs_batch_key_bits(int n_views, int size);
 int vmv_gs_batch_workspace_bytes(int n_view_gaussians, int n_instances, int key_bits, size_t* scan_bytes, size_t* sort_bytes);
 int vmv_gs_batch_preprocess(const VmvGsBatchParams* p, void* stream);
 int vmv_gs_batch_render(const VmvGsBatchParams* p, void* stream);
+
+/* The batched blend with DEPTH outputs (additive: the ABI version does not change, callers detect the entry by its symbol).  Called
+ * after vmv_gs_batch_preprocess exactly where vmv_gs_batch_render would be: the same sort, ranges and workspace rules, and out_color /
+ * out_alpha bit-identical to vmv_gs_batch_render's.  Per pixel, with the blend's own rules (skip power > 0; alpha = min(0.99, o e^power);
+ * skip alpha < 1/255; stop before the Gaussian that would take T below 1e-4) and z = the Gaussian's view depth (`depth`):
+ *   out_depth        = sum alpha_i T_i z_i — the weights of colour and alpha, NOT normalised by alpha; the background adds nothing
+ *   out_median_depth = z of the first blended Gaussian, front to back, after which the transmittance T is below 0.5; 0 if T never
+ *                      falls below 0.5 (valid depths exceed the 0.2 near cull, so 0 means "no surface")
+ * A tile or view without instances writes the background, 0 and 0.  VMV_ENULL for a null block or a null out_depth; every check of
+ * vmv_gs_batch_render applies to `pass`.  No allocation, no synchronisation. */
+typedef struct {
+    VmvGsBatchParams pass;       /* as for vmv_gs_batch_render; out_color required, out_alpha optional          */
+    float* out_depth;            /* [B * V][size][size]  sum of alpha T z (view depth), 0 where nothing blends  */
+    float* out_median_depth;     /* [B * V][size][size]  or NULL: z where T first falls below 0.5, else 0       */
+} VmvGsDepthParams;
+int vmv_gs_batch_render_depth(const VmvGsDepthParams* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Fitting Gaussians to a view set (videomv_amd/gs_fit.py): the batched pass above, differentiated.  fp32 throughout.

@@ -124,6 +124,10 @@ class GsBackwardParams(C.Structure):
                 ("grad2d", C.c_void_p), ("grad_view", C.c_void_p), ("grad", C.c_void_p)]
 
 
+class GsDepthParams(C.Structure):
+    _fields_ = [("pass_", GsBatchParams), ("out_depth", C.c_void_p), ("out_median_depth", C.c_void_p)]
+
+
 class GsAdamParams(C.Structure):
     _fields_ = [("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p), ("gaussians", C.c_void_p),
                 ("n", C.c_int32), ("step", C.c_int32), ("lr", C.c_float * 5), ("beta1", C.c_float), ("beta2", C.c_float),
@@ -221,6 +225,7 @@ SYMBOLS = {
     "vmv_gs_batch_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vmv_gs_batch_preprocess": (C.c_int, [C.POINTER(GsBatchParams), _P]),
     "vmv_gs_batch_render": (C.c_int, [C.POINTER(GsBatchParams), _P]),
+    "vmv_gs_batch_render_depth": (C.c_int, [C.POINTER(GsDepthParams), _P]),
     "vmv_gs_batch_render_state": (C.c_int, [C.POINTER(GsBackwardParams), _P]),
     "vmv_gs_batch_backward": (C.c_int, [C.POINTER(GsBackwardParams), _P]),
     "vmv_gs_image_loss": (C.c_int, [_P, _P, C.c_long, _P, _P, _P, _P]),
@@ -281,7 +286,7 @@ def load():
     if lib.vmv_elem_type() != (ELEM_F16 if _elem == "f16" else ELEM_BF16):
         raise RuntimeError(f"{LIB_PATH} was built for another element type")
     for which, st in ((OP_GEMM, GemmParams), (OP_GN_STATS, GroupNormParams), (OP_LAYERNORM, LayerNormParams),
-                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
+                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (108, GsDepthParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
         if lib.vmv_sizeof(which) != C.sizeof(st):
             raise RuntimeError(f"struct layout drift for {st.__name__}: C {lib.vmv_sizeof(which)} vs ctypes "
                                f"{C.sizeof(st)}")

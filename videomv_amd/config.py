@@ -73,6 +73,9 @@ def default_cfg() -> AttrDict:
     c.gs_orbit_views = 0              # novel views rendered around the asset (0: none)
     c.gs_orbit_elevation = None       # their elevation (None: the entrance's)
     c.gs_orbit_size = None            # their image size (None: lgm_opt.output_size)
+    c.gs_orbit_depth = False          # also write the orbit's median-depth maps: <stem>_gs_orbit_depth.npy / .png (GaussianRenderer.render_depth)
+    c.gs_points = False               # also write the point cloud those depth maps unproject to: <stem>_gs_points.ply
+    c.gs_points_voxel = None          # its merge voxel (None: 1/256 of the width the orbit camera sees at the origin's distance)
     return c
 
 

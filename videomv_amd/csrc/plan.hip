@@ -59,6 +59,7 @@ extern "C" int vmv_sizeof(int which) {
         case 105: return (int)sizeof(VmvGsBackwardParams);
         case 106: return (int)sizeof(VmvGsAdamParams);
         case 107: return (int)sizeof(VmvGsSsimLossParams);
+        case 108: return (int)sizeof(VmvGsDepthParams);
         default: return (int)op_size(which);
     }
 }

@@ -270,20 +270,35 @@ __global__ __launch_bounds__(256) void gs_ranges_kernel(const VmvGsParams p) {
 // alpha = min(0.99, opacity e^power), skip alpha < 1/255, stop BEFORE the Gaussian that would take T below 1e-4.
 // STATE (the fitter's forward, vmv_gs_batch_render_state): also write every pixel's final T and the count of the tile's instances up to and
 // including the last one it blended — what the backward pass (raster_bwd.hip) walks.  STATE = false is the production blend, unchanged.
-template <bool STATE = false, typename Order>
+// DEPTH (vmv_gs_batch_render_depth): every staged Gaussian also carries its view depth z (`depth`, the preprocess array the sort keys
+// come from; pads get 0) in one more LDS field array, and the pixel accumulates, with the SAME weights w = alpha T as colour and Wt,
+//   D   = sum w z                                   the expected depth, not normalised (oracle/gs_ref.render's third value)
+//   med = z of the first APPLIED Gaussian after which T < 0.5, else 0     the median depth; z > 0.2 always, so med == 0 is "not yet"
+// one FMA, one compare and selects per (pixel, Gaussian); the control flow stays wave-uniform.  A Gaussian that triggers the T < 1e-4
+// stop is not applied and T was below 0.01 before it, so the crossing is always recorded before a wave leaves on saturation.
+// DEPTH = false instantiates none of it: no LDS array, no registers.
+template <bool STATE = false, bool DEPTH = false, typename Order>
 VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const uint32_t lo, const uint32_t hi,
                            const Order order, const float* __restrict__ xy, const float* __restrict__ conic_opacity,
                            const float* __restrict__ gaussians, float* __restrict__ out_color, float* __restrict__ out_alpha,
-                           float* __restrict__ out_T = nullptr, int32_t* __restrict__ out_count = nullptr) {
+                           float* __restrict__ out_T = nullptr, int32_t* __restrict__ out_count = nullptr,
+                           const float* __restrict__ depth = nullptr, float* __restrict__ out_depth = nullptr,
+                           float* __restrict__ out_median = nullptr) {
     // staged Gaussians, one array per field (+ 2 pad entries): the loop takes them TWO at a time, a field pair is one ds_read_b64 and
     // the falloff exponents of the pair are packed fp32 operations (v_pk_*: 8 for two Gaussians where the one-at-a-time form issued 16)
     __shared__ __attribute__((aligned(16))) float s_x[258], s_y[258], s_A[258], s_B[258], s_C[258], s_l[258], s_o[258], s_r[258], s_g[258], s_b[258];
     __shared__ int s_done;
+    float* s_z = nullptr;
+    if constexpr (DEPTH) {
+        __shared__ __attribute__((aligned(16))) float s_zbuf[258];
+        s_z = s_zbuf;
+    }
     const int px = blockIdx.x * GS_TILE + (threadIdx.x & 15), py = blockIdx.y * GS_TILE + (threadIdx.x >> 4);
     const bool inside = px < size && py < size;
     const float fx = (float)px, fy = (float)py;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Wt = 0.f;
     int32_t last = 0;                          // (STATE only) instances [lo, lo + last) reach this pixel's last blended one
+    float D = 0.f, med = 0.f;                  // (DEPTH only)
     bool done = !inside;
     constexpr float LOG2E = 1.4426950408889634f;
     constexpr float CULL = -7.9943534f - 0.02f;      // log2(1 / 255) with a margin: the exact alpha test follows for what passes
@@ -301,10 +316,12 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
             s_l[threadIdx.x] = o > 0.f ? __builtin_amdgcn_logf(o) : -1e30f;      // v_log_f32: log2
             s_o[threadIdx.x] = o;
             s_r[threadIdx.x] = g[0]; s_g[threadIdx.x] = g[1]; s_b[threadIdx.x] = g[2];
+            if constexpr (DEPTH) s_z[threadIdx.x] = depth[gi];
         } else {                               // pad: a Gaussian nobody sees (the pair of an odd tail)
             s_x[threadIdx.x] = 0.f; s_y[threadIdx.x] = 0.f; s_A[threadIdx.x] = 0.f; s_B[threadIdx.x] = 0.f; s_C[threadIdx.x] = 0.f;
             s_l[threadIdx.x] = -1e30f; s_o[threadIdx.x] = 0.f;
             s_r[threadIdx.x] = 0.f; s_g[threadIdx.x] = 0.f; s_b[threadIdx.x] = 0.f;      // (weight 0 x stale LDS could be 0 x NaN)
+            if constexpr (DEPTH) s_z[threadIdx.x] = 0.f;
         }
         __syncthreads();
         const int n = (int)min(256u, hi - base);
@@ -320,6 +337,11 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
             C0 += s_r[k] * w; C1 += s_g[k] * w; C2 += s_b[k] * w; Wt += w;
             T = apply ? tT : T;
             if constexpr (STATE) last = apply ? (int32_t)(base - lo) + k + 1 : last;
+            if constexpr (DEPTH) {
+                const float z = s_z[k];
+                D += z * w;
+                med = (apply && tT < 0.5f && med == 0.0f) ? z : med;
+            }
         };
         const f32x2_t fx2 = {fx, fx}, fy2 = {fy, fy};
         for (int k = 0; k < n; k += 2) {       // (entry n of an odd n is a pad or, in a full batch, never read: n = 256 is even)
@@ -346,6 +368,10 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
         out_color[2 * hw + o] = fminf(1.f, fmaxf(0.f, b));
         if (out_alpha) out_alpha[o] = Wt;
         if constexpr (STATE) { out_T[o] = T; out_count[o] = last; }
+        if constexpr (DEPTH) {
+            out_depth[o] = D;
+            if (out_median) out_median[o] = med;
+        }
     }
 }
 
@@ -380,6 +406,21 @@ __global__ __launch_bounds__(256) void gs_render_batch_state_kernel(const VmvGsB
     gs_blend_tile<true>(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy + 2 * vo,
                         p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
                         p.out_alpha ? p.out_alpha + hw * vv : nullptr, final_T + hw * vv, n_contrib + hw * vv);
+}
+
+// the batched blend with the depth mode on: expected and median depth next to the same image and alpha
+__global__ __launch_bounds__(256) void gs_render_batch_depth_kernel(const VmvGsBatchParams p, float* __restrict__ out_depth,
+                                                                    float* __restrict__ out_median) {
+    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
+    const int vv = blockIdx.z;
+    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
+    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
+    // (a tile or view without instances has ranges 0 / 0: the background, D = 0, median = 0)
+    const uint32_t* vs = p.vals_sorted;
+    gs_blend_tile<false, true>(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; },
+                               p.xy + 2 * vo, p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
+                               p.out_alpha ? p.out_alpha + hw * vv : nullptr, nullptr, nullptr, p.depth + vo, out_depth + hw * vv,
+                               out_median ? out_median + hw * vv : nullptr);
 }
 
 int gs_check(const VmvGsParams& p) {
@@ -506,7 +547,7 @@ extern "C" int vmv_gs_batch_preprocess(const VmvGsBatchParams* pp, void* stream)
 }
 
 namespace {
-int gs_batch_render(const VmvGsBatchParams* pp, float* final_T, int32_t* n_contrib, void* stream) {
+int gs_batch_render(const VmvGsBatchParams* pp, float* final_T, int32_t* n_contrib, float* out_depth, float* out_median, void* stream) {
     if (!pp) return VMV_ENULL;
     const VmvGsBatchParams& p = *pp;
     int rc = gs_batch_check(p);
@@ -530,16 +571,23 @@ int gs_batch_render(const VmvGsBatchParams* pp, float* final_T, int32_t* n_contr
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(gs_ranges_batch_kernel, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st, p);
     }
-    if (final_T) hipLaunchKernelGGL(gs_render_batch_state_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, final_T, n_contrib);
+    if (out_depth) hipLaunchKernelGGL(gs_render_batch_depth_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, out_depth, out_median);
+    else if (final_T) hipLaunchKernelGGL(gs_render_batch_state_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, final_T, n_contrib);
     else hipLaunchKernelGGL(gs_render_batch_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p);
     return vmv_launch_status();
 }
 }  // namespace
 
-extern "C" int vmv_gs_batch_render(const VmvGsBatchParams* pp, void* stream) { return gs_batch_render(pp, nullptr, nullptr, stream); }
+extern "C" int vmv_gs_batch_render(const VmvGsBatchParams* pp, void* stream) { return gs_batch_render(pp, nullptr, nullptr, nullptr, nullptr, stream); }
 
 extern "C" int vmv_gs_batch_render_state(const VmvGsBackwardParams* pp, void* stream) {
     if (!pp) return VMV_ENULL;
     if (!pp->final_T || !pp->n_contrib) return VMV_ENULL;
-    return gs_batch_render(&pp->pass, pp->final_T, pp->n_contrib, stream);
+    return gs_batch_render(&pp->pass, pp->final_T, pp->n_contrib, nullptr, nullptr, stream);
+}
+
+extern "C" int vmv_gs_batch_render_depth(const VmvGsDepthParams* pp, void* stream) {
+    if (!pp) return VMV_ENULL;
+    if (!pp->out_depth) return VMV_ENULL;
+    return gs_batch_render(&pp->pass, nullptr, nullptr, pp->out_depth, pp->out_median_depth, stream);
 }

@@ -393,6 +393,14 @@ def worker_i2v(gpu, cfg, cfg_update):
 def _check_export_cfg(cfg, use_lgm):
     """`save_gaussians` (not a reference key) exports the LGM-refined loop's Gaussians: refuse it, before any sampling, where that loop
     does not run or cannot run (the LGM renders square views only), or where the fit's objective is not one the fitter knows."""
+    geometry = [k for k in ('gs_orbit_depth', 'gs_points', 'gs_points_voxel') if cfg.get(k)]
+    if geometry and not (cfg.get('save_gaussians') and int(cfg.get('gs_orbit_views') or 0) > 0):
+        raise ValueError(f"{' / '.join(geometry)}: depth maps and the point cloud come from the orbit render of the exported Gaussians: "
+                         "set save_gaussians True and gs_orbit_views > 0")
+    if cfg.get('gs_points_voxel') and not cfg.get('gs_points'):
+        raise ValueError("gs_points_voxel is the voxel size of the gs_points export: set gs_points True")
+    if cfg.get('gs_points_voxel') is not None and cfg.get('gs_points') and not float(cfg.get('gs_points_voxel')) > 0:
+        raise ValueError(f"gs_points_voxel must be positive, got {cfg.get('gs_points_voxel')}")
     if not cfg.get('save_gaussians'):
         return
     if not use_lgm:
@@ -416,7 +424,9 @@ def _fit_loss(cfg):
 def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist, stem, device):
     """The 3-D asset of one LGM-refined sample: the LGM on its final key views (LgmRefiner.gaussians_from_views), optionally fitted to
     all its decoded views (gs_fit.GaussianFitter: targets video * 0.5 + 0.5 against the refiner's background), written as
-    ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit.  Draws nothing from
+    ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit; with ``gs_orbit_depth``
+    / ``gs_points`` that orbit is rendered ONCE in the rasteriser's depth mode and its median-depth maps (``_gs_orbit_depth.npy`` /
+    ``.png``) and the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) are written too.  Draws nothing from
     the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
     from .gs import GaussianRenderer
     from .lgm import orbit_cameras
@@ -451,14 +461,61 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
         size = int(cfg.get('gs_orbit_size') or opt.output_size)
         cv, cvp = orbit_cameras(camera_data, n_orbit, elev, camera_dist, opt)
         bgc = torch.full((3,), refiner.bg_color, dtype=torch.float32, device=device)
-        img = GaussianRenderer(size, opt.fovy, opt.znear, opt.zfar).render(g.to(device), cv.to(device), cvp.to(device), None,
-                                                                          bg_color=bgc)["image"]
+        renderer = GaussianRenderer(size, opt.fovy, opt.znear, opt.zfar)
+        geometry = bool(cfg.get('gs_orbit_depth') or cfg.get('gs_points'))
+        out = (renderer.render_depth if geometry else renderer.render)(g.to(device), cv.to(device), cvp.to(device), None, bg_color=bgc)
+        img = out["image"]
         mean, std = torch.tensor(cfg.mean).view(1, 3, 1, 1, 1), torch.tensor(cfg.std).view(1, 3, 1, 1, 1)
         video = (img.float().cpu().permute(0, 2, 1, 3, 4) - mean) / std                 # [1, 3, n, S, S], the entrance's range
         rec['orbit_sheet'], rec['orbit_frames'] = stem + '_gs_orbit.png', stem + '_gs_orbit'
         _save_contact_sheet(video, rec['orbit_sheet'], cfg.mean, cfg.std)
         _save_frames_safe(stem + '_gs_orbit.mp4', video, cfg)
+        if cfg.get('gs_orbit_depth'):
+            rec['orbit_depth'], rec['orbit_depth_sheet'] = stem + '_gs_orbit_depth.npy', stem + '_gs_orbit_depth.png'
+            _save_depth_maps(out["median_depth"][0, :, 0].float().cpu(), rec['orbit_depth'], rec['orbit_depth_sheet'], opt.znear, opt.zfar)
+            logging.info(f"Save {n_orbit} median-depth maps to {rec['orbit_depth']}")
+        if cfg.get('gs_points'):
+            voxel = cfg.get('gs_points_voxel')
+            # default: 1/256 of the camera extent = the width the first orbit camera sees at its distance from the origin of the Gaussians' frame
+            extent = 2.0 * renderer.tan_half_fov * float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
+            voxel = extent / 256.0 if voxel is None else float(voxel)
+            rec['points_ply'] = stem + '_gs_points.ply'
+            rec['points'] = _export_points(out, cv[0], renderer.tan_half_fov, refiner.bg_color, voxel, rec['points_ply'])
+            logging.info(f"Save point cloud ({rec['points']} points, voxel {voxel:.5f}) to {rec['points_ply']}")
     return rec
+
+
+def _save_depth_maps(depth, npy_path, png_path, znear, zfar):
+    """depth [n, S, S] (median depth, 0 = no surface) -> the float32 array as .npy and an 8-bit contact sheet: znear .. zfar mapped
+    linearly to white .. black, no-surface pixels black."""
+    import numpy as np
+    d = depth.numpy().astype(np.float32)
+    np.save(npy_path, d)
+    try:
+        from PIL import Image
+        shade = np.clip((zfar - d) / (zfar - znear), 0.0, 1.0)
+        shade[d <= 0] = 0.0
+        Image.fromarray(np.concatenate(list(np.round(shade * 255.0).astype(np.uint8)), axis=1)).save(png_path)
+    except Exception as e:  # pragma: no cover
+        logging.info(f'Step: save png error with {e}')
+
+
+def _export_points(out, cam_view, tan_half_fov, bg, voxel, path):
+    """The pixels of every view of ``out`` (GaussianRenderer.render_depth, sample 0) that have a median depth, unprojected to world
+    points and coloured with the un-premultiplied render clamp((image - (1 - alpha) bg) / alpha, 0, 1), merged per voxel, written as a
+    .ply.  Deterministic, no RNG.  -> the number of points."""
+    from .gs import depth_to_points, merge_points_voxel, save_points_ply
+    pts, cols = [], []
+    for v in range(cam_view.shape[0]):
+        p, idx = depth_to_points(out["median_depth"][0, v, 0], cam_view[v], tan_half_fov)
+        a = out["alpha"][0, v, 0].reshape(-1)[idx]
+        c = out["image"][0, v].reshape(3, -1)[:, idx]
+        pts.append(p)
+        cols.append(((c - (1.0 - a) * bg) / a.clamp_min(1e-6)).clamp(0, 1).t())
+    pts, cols = torch.cat(pts).float().cpu(), torch.cat(cols).float().cpu()
+    if pts.shape[0] > 0:
+        pts, cols = merge_points_voxel(pts, cols, voxel)
+    return save_points_ply(pts, cols, path)
 
 
 def _save_frames_safe(local_path, video, cfg):

@@ -7,6 +7,8 @@ the view in the key, one blend launch over tiles x views) and the host reads the
 per LGM-refined step in round 4, one now (``VMV_GS_BATCH=0`` restores the per-view loop; both share their device code and give the
 same bits).  The reference delegates to the third-party ``diff_gaussian_rasterization`` extension, which is absent and unpinned; the
 kernels follow the published forward algorithm (oracle/gs_ref.py, parity unpinned — DESIGN.md §2).
+``render_depth`` is the same batched pass with the blend's depth mode (the extension's ``rendered_depth`` and a median depth per pixel);
+``depth_to_points`` / ``merge_points_voxel`` / ``save_points_ply`` turn its maps into a coloured point cloud.
 """
 import ctypes as C
 import math
@@ -16,6 +18,66 @@ import torch
 
 from . import _lib as L
 from .ops import _stream_ptr
+
+
+def depth_to_points(depth, cam_view, tan_half_fov, mask=None):
+    """Unproject one depth map [S, S] (view depth z per pixel, 0 = nothing) to world points with the rasteriser's pixel convention:
+    a Gaussian's centre lands on px = ((ndc + 1) S - 1) / 2 at INTEGER pixel coordinates, so pixel px looks along
+    ndc = (2 px + 1) / S - 1 and x_view = z tan ndc_x (likewise y); then [x, y, z, 1] @ inverse(cam_view) (row-vector convention).
+    Keeps the pixels with depth > 0 (and ``mask``, if given).  -> (points [n, 3], flat indices [n] of the pixels kept, row-major)."""
+    S = depth.shape[-1]
+    z = depth.reshape(S, S).to(torch.float32)
+    keep = z > 0
+    if mask is not None:
+        keep = keep & mask.reshape(S, S).to(keep.device)
+    idx = torch.nonzero(keep.reshape(-1)).flatten()
+    zk = z.reshape(-1)[idx]
+    ndc_x = (2.0 * (idx % S).to(torch.float32) + 1.0) / S - 1.0
+    ndc_y = (2.0 * torch.div(idx, S, rounding_mode="floor").to(torch.float32) + 1.0) / S - 1.0
+    pv = torch.stack([zk * tan_half_fov * ndc_x, zk * tan_half_fov * ndc_y, zk, torch.ones_like(zk)], dim=1)
+    c2w = torch.inverse(cam_view.to(torch.float32).cpu()).to(z.device)
+    return (pv @ c2w)[:, :3], idx
+
+
+def merge_points_voxel(points, colours, voxel):
+    """One point per occupied cube of side ``voxel``: the mean position and the mean colour of the points inside (no RNG, order of
+    torch.unique).  points [n, 3], colours [n, 3] -> ([m, 3], [m, 3])."""
+    q = torch.floor(points / voxel).to(torch.int64)
+    _, inv, counts = torch.unique(q, dim=0, return_inverse=True, return_counts=True)
+    m = counts.shape[0]
+    both = torch.zeros(m, 6, dtype=torch.float32, device=points.device)
+    both.index_add_(0, inv, torch.cat([points.float(), colours.float()], dim=1))
+    both = both / counts.to(torch.float32).unsqueeze(1)
+    return both[:, :3], both[:, 3:]
+
+
+def save_points_ply(points, colours, path):
+    """points [n, 3] fp32, colours [n, 3] in [0, 1] -> binary little-endian .ply: x y z float32, red green blue uchar (rounded).
+    Returns the number of vertices written."""
+    n = int(points.shape[0])
+    rows = np.empty(n, dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)])
+    rows["xyz"] = points.detach().float().cpu().numpy()
+    rows["rgb"] = (colours.detach().float().cpu().clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).numpy()
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n
+    header += "".join("property float %s\n" % a for a in "xyz") + "".join("property uchar %s\n" % a for a in ("red", "green", "blue"))
+    with open(path, "wb") as f:
+        f.write((header + "end_header\n").encode("ascii"))
+        f.write(rows.tobytes())
+    return n
+
+
+def load_points_ply(path):
+    """The inverse of ``save_points_ply`` -> (points [n, 3] fp32, colours [n, 3] uint8)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    props = [ln.split()[1:] for ln in lines if ln.startswith("property")]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or props != [["float", a] for a in "xyz"] + [["uchar", a] for a in ("red", "green", "blue")]:
+        raise ValueError(f"{path}: not a point cloud written by save_points_ply")
+    n = int(next(ln for ln in lines if ln.startswith("element vertex")).split()[2])
+    rows = np.frombuffer(data, dtype=[("xyz", "<f4", 3), ("rgb", "u1", 3)], count=n, offset=end)
+    return torch.from_numpy(rows["xyz"].copy()), torch.from_numpy(rows["rgb"].copy())
 
 
 class GaussianRenderer:
@@ -75,8 +137,9 @@ class GaussianRenderer:
             self._buf[key] = b
         return b
 
-    def _render_batch(self, gaussians, cam_view, cam_view_proj, bg, images, alphas):
-        """All B * V views in one pass (vmv.h VmvGsBatchParams)."""
+    def _render_batch(self, gaussians, cam_view, cam_view_proj, bg, images, alphas, depths=None, medians=None):
+        """All B * V views in one pass (vmv.h VmvGsBatchParams); with ``depths`` / ``medians`` the blend is the depth mode's
+        (VmvGsDepthParams: the same pass, the same image and alpha bits)."""
         device = gaussians.device
         B, V = cam_view.shape[:2]
         N, S = gaussians.shape[1], self.size
@@ -85,7 +148,8 @@ class GaussianRenderer:
         g = gaussians.float().contiguous()
         views = cam_view.to(device, torch.float32).reshape(B * V, 16).contiguous()
         vps = cam_view_proj.to(device, torch.float32).reshape(B * V, 16).contiguous()
-        p = L.GsBatchParams()
+        dp = L.GsDepthParams()
+        p = dp.pass_
         p.gaussians, p.B, p.N, p.V, p.size = g.data_ptr(), B, N, V, S
         p.views, p.view_projs, p.tan_half_fov = views.data_ptr(), vps.data_ptr(), self.tan_half_fov
         p.bg[0], p.bg[1], p.bg[2] = bg
@@ -118,27 +182,56 @@ class GaussianRenderer:
             p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
         p.ranges = buf["ranges"].data_ptr()
         p.out_color, p.out_alpha = images.data_ptr(), alphas.data_ptr()
-        L.check(lib.vmv_gs_batch_render(C.byref(p), _stream_ptr()), "gs_batch_render")
+        if depths is None:
+            L.check(lib.vmv_gs_batch_render(C.byref(p), _stream_ptr()), "gs_batch_render")
+        else:
+            dp.out_depth, dp.out_median_depth = depths.data_ptr(), None if medians is None else medians.data_ptr()
+            L.check(lib.vmv_gs_batch_render_depth(C.byref(dp), _stream_ptr()), "gs_batch_render_depth")
         self._keep.append((g, views, vps))    # (referenced by the enqueued launches)
         return True
 
-    def _render_views(self, gaussians, cam_view, cam_view_proj, bg, images, alphas):
+    def _render_views(self, gaussians, cam_view, cam_view_proj, bg, *outs):
         """The batched pass over as many views at a time as its 32-bit instance count and the memory budget allow: all B * V at once when
         they fit (the VideoMV shapes: 2 x 24 views, 21 M instances), else per sample, else halves of a sample's views; a single view that
-        still does not fit goes to the per-view entry points.  Chunks are independent renders: images are those of the one-pass call."""
+        still does not fit goes to the per-view entry points.  Chunks are independent renders: images are those of the one-pass call.
+        ``outs`` = the [B, V, ...] output tensors of ``_render_batch`` (images, alphas and, in the depth mode, depths, medians)."""
         B, V = cam_view.shape[:2]
         N, tiles = gaussians.shape[1], ((self.size + 15) // 16) ** 2
         if B * V * N * tiles < (1 << 32) and B * V * N < (1 << 31) and B * V <= 65535:
-            if self._render_batch(gaussians, cam_view, cam_view_proj, bg, images, alphas):
+            if self._render_batch(gaussians, cam_view, cam_view_proj, bg, *outs):
                 return True
         if B > 1:
-            return all(self._render_views(gaussians[b:b + 1], cam_view[b:b + 1], cam_view_proj[b:b + 1], bg, images[b:b + 1], alphas[b:b + 1])
+            return all(self._render_views(gaussians[b:b + 1], cam_view[b:b + 1], cam_view_proj[b:b + 1], bg, *(o[b:b + 1] for o in outs))
                        for b in range(B))
         if V > 1:
             h = V // 2
-            return all(self._render_views(gaussians, cam_view[:, a:z], cam_view_proj[:, a:z], bg, images[:, a:z], alphas[:, a:z])
+            return all(self._render_views(gaussians, cam_view[:, a:z], cam_view_proj[:, a:z], bg, *(o[:, a:z] for o in outs))
                        for a, z in ((0, h), (h, V)))
         return False
+
+    def _begin(self, gaussians, cam_view, bg_color, planes):
+        """Common start of ``render`` / ``render_depth``: the background, one empty [B, V, c, S, S] fp32 output per entry of ``planes``,
+        the per-call records and the instance budget."""
+        import os
+        B, V = cam_view.shape[:2]
+        bg = [1.0, 1.0, 1.0] if bg_color is None else [float(v) for v in bg_color.reshape(-1)[:3]]
+        outs = [torch.empty(B, V, c, self.size, self.size, dtype=torch.float32, device=gaussians.device) for c in planes]
+        self.last_num_rendered, self.last_views, self._keep = [], B * V, []
+        self.max_batch_instances = min((1 << 31) - 1, int(os.environ.get("VMV_GS_BATCH_MAX_INSTANCES", str(1 << 28))))   # 2^28 x 30 B = 8 GB
+        return bg, outs
+
+    @torch.no_grad()
+    def render_depth(self, gaussians, cam_view, cam_view_proj, cam_pos=None, bg_color=None):
+        """``render`` plus geometry, through the batched pass's depth mode (vmv_gs_batch_render_depth; chunked like ``render``):
+        -> ``{"image", "alpha"}`` with ``render``'s bits, ``"depth"`` [B,V,1,S,S] = sum alpha T z over the blended Gaussians (view depth,
+        not normalised: the extension's ``rendered_depth``) and ``"median_depth"`` [B,V,1,S,S] = z of the first blended Gaussian after
+        which the transmittance is below 0.5, 0 where it never is.  The per-view entry points have no depth mode: a single view whose
+        instances pass VMV_GS_BATCH_MAX_INSTANCES is refused."""
+        bg, outs = self._begin(gaussians, cam_view, bg_color, (3, 1, 1, 1))
+        if not self._render_views(gaussians, cam_view, cam_view_proj, bg, *outs):
+            raise NotImplementedError("render_depth: a single view does not fit the batched pass (VMV_GS_BATCH_MAX_INSTANCES = "
+                                      f"{self.max_batch_instances}) and the per-view entry points have no depth mode")
+        return dict(zip(("image", "alpha", "depth", "median_depth"), outs))
 
     @torch.no_grad()
     def render(self, gaussians, cam_view, cam_view_proj, cam_pos=None, bg_color=None, scale_modifier=1):
@@ -149,11 +242,7 @@ class GaussianRenderer:
         B, V = cam_view.shape[:2]
         N, S = gaussians.shape[1], self.size
         lib = L.load()
-        bg = [1.0, 1.0, 1.0] if bg_color is None else [float(v) for v in bg_color.reshape(-1)[:3]]
-        images = torch.empty(B, V, 3, S, S, dtype=torch.float32, device=device)
-        alphas = torch.empty(B, V, 1, S, S, dtype=torch.float32, device=device)
-        self.last_num_rendered, self.last_views, self._keep = [], B * V, []
-        self.max_batch_instances = min((1 << 31) - 1, int(os.environ.get("VMV_GS_BATCH_MAX_INSTANCES", str(1 << 28))))   # 2^28 x 30 B = 8 GB
+        bg, (images, alphas) = self._begin(gaussians, cam_view, bg_color, (3, 1))
         if os.environ.get("VMV_GS_BATCH", "1") != "0":
             if self._render_views(gaussians, cam_view, cam_view_proj, bg, images, alphas):
                 return {"image": images, "alpha": alphas}
