@@ -28,15 +28,16 @@
 // no MFMAs 314 us, GELU -> identity 336 us, no barrier / DMA 308 us, deeper fragment prefetch (2 k-steps / 6 tiles, 3 / 8) 390 /
 // 395 us.  The way forward is 32 x 32 x 16 MFMAs over 32 rows per wave PAIR with the output columns split between the two waves
 // and the hidden chunk exchanged through LDS (half the fragment bytes per MFMA); 80 + 80 + 32 registers — not built.
-#include "gemm_glds_common.h"
+#include "gemm_rs_common.h"
 
 using namespace vmvg;
 
 namespace {
 
-constexpr int FF_C = 320, FF_KS = FF_C / 32, FF_NT = FF_C / 16;       // channels, k-steps of FF1, output tiles of FF2
+using FfW1 = RsRing<10>;                                                 // the W1 image of a chunk: 64 rows x 640 B, one ring slot of gemm_rs_common.h
+constexpr int FF_C = FfW1::K, FF_KS = FfW1::KS, FF_NT = FF_C / 16;      // channels, k-steps of FF1, output tiles of FF2
 constexpr int FF_HC = 32;                                                // hidden channels per chunk
-constexpr int FF_W1_BYTES = 2 * FF_HC * FF_C * 2;                        // 64 rows x 640 B
+constexpr int FF_W1_BYTES = FfW1::CHUNK_BYTES;
 constexpr int FF_W2_BYTES = FF_C * FF_HC * 2;                            // 320 rows x 64 B
 constexpr int FF_STAGE = FF_W1_BYTES + FF_W2_BYTES;                      // 61 440
 constexpr int FF_B1_BYTES = 8 * FF_C * 4, FF_B2_BYTES = FF_C * 4;
@@ -45,12 +46,6 @@ static_assert(FF_LDS <= 160 * 1024, "LDS budget");
 
 constexpr int FF_PF1 = 1;       // FF1 fragment prefetch distance in k-steps (4 fragments each)
 constexpr int FF_PF2 = 3;       // FF2 fragment prefetch distance in output tiles
-
-VMV_DEV u32x4_t ff_swap16_xz_yw(u32x4_t v) {         // (gemm_rs.hip: padded v_permlane16_swap pair)
-    uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-    asm("s_nop 3\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));
-    return u32x4_t{x, y, z, w};
-}
 
 __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
     VMV_KERNEL_ENTER();
@@ -87,16 +82,10 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
     const int w2_slot = (lane & 3) ^ ((0x78 >> (2 * ((lane >> 4) & 3))) & 3);
     auto issue_chunk = [&](int c, int slot) {
         unsigned char* base = smem + slot * FF_STAGE;
-        {   // W1: wave w fills bytes [5120 w, 5120 (w + 1)) of the 40-KB image (64 rows x 40 slots), k-slot s ^ ((r >> 1) & 7) at (r, s)
+        {   // W1: 64 rows of the chunk's image
+            unsigned char* w1 = FfW1::wave_base(base, wave);
             const uint32_t so = (uint32_t)(c * 2 * FF_HC * FF_C) * 2u;
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const int u = wave * 320 + q * 64 + ln;
-                const int r = u / 40, s = u - r * 40;
-                blds16(w1_rsrc, base + wave * 5120 + q * 1024, (uint32_t)(r * FF_C + (s ^ ((r >> 1) & 7)) * 8) * 2u, so);
-            }
+            rs_issue_rows<FfW1>(w1_rsrc, w1, wave, lane, so, [&](const int r) { return r * FF_C; });
         }
         {   // W2: 20 pieces, wave w takes w, w + 8, w + 16
             const uint32_t so = (uint32_t)(c * FF_HC) * 2u;
@@ -106,50 +95,17 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
     };
     issue_chunk(0, 0);
 
-    // ---- LayerNorm of the resident rows (two-pass, fp32; gemm_rs.hip)
-    if (p.ln_eps > 0.f) {
-        const float inv_k = 1.0f / (float)FF_C;
-        float s1 = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < FF_KS; ++kk) {
-            elem_dot2c(s1, a[kk].x, VMV_ELEM_ONE2); elem_dot2c(s1, a[kk].y, VMV_ELEM_ONE2);
-            elem_dot2c(s1, a[kk].z, VMV_ELEM_ONE2); elem_dot2c(s1, a[kk].w, VMV_ELEM_ONE2);
-        }
-        asm volatile("s_nop 4" : "+v"(s1));          // (DOT result -> VALU read: gemm_rs.hip)
-        const float mean = xor16_32_sum(s1) * inv_k;
-        float s2 = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < FF_KS; ++kk) {
-            const uint32_t w4[4] = {a[kk].x, a[kk].y, a[kk].z, a[kk].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d0 = elem_lo(w4[e]) - mean, d1 = elem_hi(w4[e]) - mean;
-                s2 = fmaf(d0, d0, s2); s2 = fmaf(d1, d1, s2);
-            }
-        }
-        const float rstd = __builtin_amdgcn_rsqf(xor16_32_sum(s2) * inv_k + p.ln_eps);
-        const float nm = -mean * rstd;
-#pragma unroll
-        for (int kk = 0; kk < FF_KS; ++kk) asm volatile("" : "+v"(a[kk].x), "+v"(a[kk].y), "+v"(a[kk].z), "+v"(a[kk].w));
-#pragma unroll
-        for (int kk = 0; kk < FF_KS; ++kk) {
-            a[kk].x = pack_elem2(fmaf(elem_lo(a[kk].x), rstd, nm), fmaf(elem_hi(a[kk].x), rstd, nm));
-            a[kk].y = pack_elem2(fmaf(elem_lo(a[kk].y), rstd, nm), fmaf(elem_hi(a[kk].y), rstd, nm));
-            a[kk].z = pack_elem2(fmaf(elem_lo(a[kk].z), rstd, nm), fmaf(elem_hi(a[kk].z), rstd, nm));
-            a[kk].w = pack_elem2(fmaf(elem_lo(a[kk].w), rstd, nm), fmaf(elem_hi(a[kk].w), rstd, nm));
-        }
-    }
+    // ---- LayerNorm of the resident rows
+    if (p.ln_eps > 0.f) rs_layernorm_rows(a, p.ln_eps);
 
     f32x4_t out[FF_NT];
 #pragma unroll
     for (int j = 0; j < FF_NT; ++j) out[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // fragment addressing.  W1 image: rows of 640 B, k-slot (4 kk + fgrp) ^ ((frow >> 1) & 7) (gemm_rs.hip: two lane offsets, one
-    // per kk parity, every read base + 64 kk).  W2 image: rows of 64 B, k-slot fgrp ^ T[(frow >> 2) & 3].
-    const int fsw = (frow >> 1) & 7;
-    int foff[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) foff[r] = frow * 640 + (fgrp ^ (fsw & 3)) * 16 + ((r ^ (fsw >> 2)) - r) * 64;
+    // fragment addressing.  W1 image: rs_frag_offsets (two lane offsets, one per kk parity, every read base + 64 kk).  W2 image:
+    // rows of 64 B, k-slot fgrp ^ T[(frow >> 2) & 3].
+    int foff[FfW1::NB];
+    rs_frag_offsets<FfW1>(frow, fgrp, foff);
     const int f2off = frow * 64 + (fgrp ^ ((0x78 >> (2 * ((frow >> 2) & 3))) & 3)) * 16;
 
     for (int c = 0; c < nchunk; ++c) {
@@ -215,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         }
     }
 
-    // ---- epilogue: + b2 + residual, 16-byte stores through the lane swap of gemm_rs.hip (two output tiles per store)
+    // ---- epilogue: + b2 + residual, 16-byte stores through the lane swap (rs_store16: two output tiles per store)
     const int lanecol = (fgrp & 1) * 16 + (fgrp >> 1) * 8;
     const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, SRD_RECORDS, SRD_FLAGS);
     const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.residual), 0, SRD_RECORDS, SRD_FLAGS);
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
     const uint32_t rvo = (ok && p.residual) ? (uint32_t)((m_wave + frow) * p.ldr + lanecol) * 2u : OOB;
 #pragma unroll
     for (int jp = 0; jp < FF_NT / 2; ++jp) {
-        const u32x4_t rr = ff_swap16_xz_yw(__builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvo, (uint32_t)(32 * jp) * 2u, 0));
+        const u32x4_t rr = rs_swap16(__builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvo, (uint32_t)(32 * jp) * 2u, 0));
         f32x4_t v0 = out[2 * jp] + *reinterpret_cast<const f32x4_t*>(b2_lds + 32 * jp + 4 * fgrp);
         f32x4_t v1 = out[2 * jp + 1] + *reinterpret_cast<const f32x4_t*>(b2_lds + 32 * jp + 16 + 4 * fgrp);
         v0.x += elem_lo(rr.x); v0.y += elem_hi(rr.x); v0.z += elem_lo(rr.y); v0.w += elem_hi(rr.y);
@@ -232,9 +188,7 @@ __global__ __launch_bounds__(512, 1) void ff_fused_kernel(const VmvFfParams p) {
         u32x4_t o;
         o.x = pack_elem2(v0.x, v0.y); o.y = pack_elem2(v0.z, v0.w);
         o.z = pack_elem2(v1.x, v1.y); o.w = pack_elem2(v1.z, v1.w);
-        o = ff_swap16_xz_yw(o);
-        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, ovo, (uint32_t)(32 * jp) * 2u, 0);
-        asm volatile("s_nop 7" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w) : "memory");       // (store-data discipline: gemm_rs.hip)
+        rs_store16(rs_swap16(o), out_rsrc, ovo, (uint32_t)(32 * jp) * 2u);
     }
 }
 

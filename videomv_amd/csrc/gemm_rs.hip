@@ -19,7 +19,8 @@
 //     two-pass statistics from the registers, x <- (x - mean) * rstd, then the plain product with W' = W diag(gamma) —
 //     no statistics launch, no rowstat traffic, no colsum correction in the epilogue.
 // One barrier per chunk (160 MFMAs per wave); the ring runs two chunks ahead.
-#include "gemm_glds_common.h"
+// The ring, the MFMA pair, the LayerNorm of the resident rows and the store path are gemm_rs_common.h's, shared with gemm_ff / gemm_tqa / gemm_trs.
+#include "gemm_rs_common.h"
 #include <type_traits>
 
 using namespace vmvg;
@@ -27,39 +28,16 @@ using namespace vmvg;
 namespace {
 
 template <int RT, int KS>
-struct RsCfg {
-    static constexpr int NW = 8, NT = 512;
-    static constexpr int BM = NW * RT * 16;                    // rows per block
-    static constexpr int K = KS * 32;
-    static constexpr int RB = K * 2;                           // bytes per W row
-    static constexpr int SPR = RB / 16;                        // 16-byte slots per W row (40 / 80)
-    static constexpr int CHUNK_BYTES = KS == 16 ? 32768 : 40960;   // whole W rows: 64 x 640 B, 32 x 1280 B, 32 x 1024 B (K = 512: round 6)
-    static constexpr int CROWS = CHUNK_BYTES / RB;             // W rows per chunk (64 / 32)
-    static constexpr int G = CROWS / 16;                       // 16-row W tiles per chunk (4 / 2)
-    static constexpr int STAGES = 3;
-    static constexpr int PIECES = CHUNK_BYTES / 1024 / NW;     // LDS-DMA wave-instructions per wave per chunk (5; 4 at K = 512)
+struct RsCfg : RsRing<KS> {
+    using Ring = RsRing<KS>;
+    static constexpr int BM = Ring::NW * RT * 16;              // rows per block
     static constexpr int MAX_COLS = 5120;                      // W rows one block walks (bias strip: 20 KB)
-    static constexpr int TAB_BYTES = 2 * 2 * K * 4;            // folded GroupNorm: (scale | shift)[K] fp32 of the two stat groups a block can touch
-    static constexpr int LDS_BYTES = STAGES * CHUNK_BYTES + MAX_COLS * 4 + TAB_BYTES;
-    static_assert(CROWS * RB == CHUNK_BYTES && (G == 2 || G == 4) && PIECES * NW * 1024 == CHUNK_BYTES, "chunk geometry");
+    static constexpr int TAB_BYTES = 2 * 2 * Ring::K * 4;      // folded GroupNorm: (scale | shift)[K] fp32 of the two stat groups a block can touch
+    static constexpr int LDS_BYTES = Ring::STAGES * Ring::CHUNK_BYTES + MAX_COLS * 4 + TAB_BYTES;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-// v_permlane16_swap on the dword pairs (x, z) and (y, w): lanes 16-31 / 48-63 of the first dword trade places with lanes
-// 0-15 / 32-47 of the second (an involution: applied twice it is the identity).
-// Inline asm with its own wait states: the builtin form compiled to `v_cvt_pk v191 / s_nop 0 / swap v188, v190 / swap v189, v191`,
-// and on gfx950 the second swap then read the OLD v191 in the last four lanes of each half-wave (lanes 28-31, 60-63: output
-// channels 2-3 of rows 12-15 of a tile came out as garbage, every launch) — hipcc's hazard pad for "VALU write -> v_permlane*_swap
-// read" is one state short when another swap sits in between.  Four states in front cover both swaps; the operands of the
-// asm statement are opaque to the scheduler, so nothing can slide in between.
-VMV_DEV u32x4_t swap16_xz_yw(u32x4_t v) {
-    uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-    asm("s_nop 3\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));
-    return u32x4_t{x, y, z, w};
-}
-
 constexpr int RS_GEGLU = 1, RS_LN = 2, RS_RES = 4, RS_GN = 8;
-constexpr int RS_PFD = 1;       // W-fragment prefetch distance in k-steps
 
 template <int RT, int KS, int MODE>
 __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, const int tiles_m, const int nsplit, const int cols_per_split) {
@@ -94,12 +72,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
         for (int kk = 0; kk < KS; ++kk) a[i][kk] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, vo + (uint32_t)(kk * 64), 0, 0);
     }
 
-    // ---- loader: bias strip, then the W ring.  A chunk is CROWS whole rows of W (40 KB); wave w fills bytes [5120 w, 5120 (w + 1))
-    //      of it with 5 wave-instructions.  LDS position (row r, 16-byte slot s') holds k-slot s' ^ swz(r) of that row, applied
-    //      to the SOURCE address (the image of a DMA is lane-linear): with 640-byte rows the 16 rows of a fragment alternate
-    //      between the two halves of the 256-byte bank row, so swz = (r >> 1) & 7 spreads them over all 16 16-byte units; with
-    //      1280-byte rows every row starts on the same bank, swz = r & 15.  Both are conflict-free for ds_read_b128's
-    //      non-contiguous 16-lane groups (rows {0-3, 12-15} with k-slot f, rows {4-11} with f ^ 1).
+    // ---- loader: bias strip, then the W ring (gemm_rs_common.h: a chunk is CROWS whole rows of W, swizzled on the SOURCE address)
     float* bias_lds = reinterpret_cast<float*>(smem + Cfg::STAGES * Cfg::CHUNK_BYTES);
     {
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (uint32_t)p.N * 4u : 0u, SRD_FLAGS);
@@ -119,19 +92,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     }
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     auto issue_chunk = [&](int c, int slot) {
-        unsigned char* base = smem + slot * Cfg::CHUNK_BYTES + wave * (P * 1024);
+        unsigned char* base = Cfg::wave_base(smem + slot * Cfg::CHUNK_BYTES, wave);
         const uint32_t so = (uint32_t)((n_begin + c * Cfg::CROWS) * p.ktot) * 2u;
-        // (the five source offsets are recomputed per chunk — ~30 VALU operations per 160+ MFMAs — instead of living in five
-        //  registers next to 160 of resident rows; the empty asm keeps the compiler from hoisting them out of the loop again)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int u = wave * (P * 64) + q * 64 + ln;
-            const int r = u / Cfg::SPR, s = u - r * Cfg::SPR;
-            const int sw = KS == 10 ? ((r >> 1) & 7) : (r & 15);
-            blds16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
-        }
+        rs_issue_rows<Cfg>(w_rsrc, base, wave, lane, so, [&](const int r) { return r * p.ktot; });
     };
     const int pro = NC < Cfg::STAGES ? NC : Cfg::STAGES;
     for (int c = 0; c < pro; ++c) issue_chunk(c, c);
@@ -176,48 +139,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
         }
     }
 
-    // ---- LayerNorm of the resident rows (two-pass, fp32): lanes frow, frow + 16, + 32, + 48 hold the four k-quarters of a row
-    if constexpr (LN) {
-        const float inv_k = 1.0f / (float)Cfg::K;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            float s1 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                elem_dot2c(s1, a[i][kk].x, VMV_ELEM_ONE2); elem_dot2c(s1, a[i][kk].y, VMV_ELEM_ONE2);
-                elem_dot2c(s1, a[i][kk].z, VMV_ELEM_ONE2); elem_dot2c(s1, a[i][kk].w, VMV_ELEM_ONE2);
-            }
-            // (v_dot2c is a DOT-pipe instruction: on gfx940+ its result needs 3-4 wait states before a different VALU reads it,
-            //  and hipcc pads nothing for an instruction it only sees as inline asm — without this the next v_mov picked up a
-            //  stale partial sum: means off by ~1e-2 sigma on the first GPU run)
-            asm volatile("s_nop 4" : "+v"(s1));
-            const float mean = xor16_32_sum(s1) * inv_k;
-            float s2 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const uint32_t w4[4] = {a[i][kk].x, a[i][kk].y, a[i][kk].z, a[i][kk].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d0 = elem_lo(w4[e]) - mean, d1 = elem_hi(w4[e]) - mean;
-                    s2 = fmaf(d0, d0, s2); s2 = fmaf(d1, d1, s2);
-                }
-            }
-            const float rstd = __builtin_amdgcn_rsqf(xor16_32_sum(s2) * inv_k + p.ln_eps);
-            const float nm = -mean * rstd;
-            // (the normalisation pass unpacks the same registers as the variance pass: left visible, the compiler keeps the 80
-            //  unpacked fp32 values of the row tile alive in between — the bf16 build, whose unpack is a shift, spilled 300
-            //  registers that way — so the packed registers are made opaque here)
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) asm volatile("" : "+v"(a[i][kk].x), "+v"(a[i][kk].y), "+v"(a[i][kk].z), "+v"(a[i][kk].w));
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                a[i][kk].x = pack_elem2(fmaf(elem_lo(a[i][kk].x), rstd, nm), fmaf(elem_hi(a[i][kk].x), rstd, nm));
-                a[i][kk].y = pack_elem2(fmaf(elem_lo(a[i][kk].y), rstd, nm), fmaf(elem_hi(a[i][kk].y), rstd, nm));
-                a[i][kk].z = pack_elem2(fmaf(elem_lo(a[i][kk].z), rstd, nm), fmaf(elem_hi(a[i][kk].z), rstd, nm));
-                a[i][kk].w = pack_elem2(fmaf(elem_lo(a[i][kk].w), rstd, nm), fmaf(elem_hi(a[i][kk].w), rstd, nm));
-            }
-        }
-    }
+    if constexpr (LN) rs_layernorm_rows(a, p.ln_eps);
 
     // ---- output / residual addressing: after the lane swaps a lane holds 8 consecutive channels of row frow:
     //      columns (fgrp & 1) * 16 + (fgrp >> 1) * 8 .. + 8 of the 32-column pair
@@ -237,46 +159,16 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    // fragment addressing: this lane's rows 16 j + frow have swz = fsw (lane constant); k-slot (4 kk + fgrp) ^ fsw =
-    // 4 (kk ^ (fsw >> 2)) + (fgrp ^ (fsw & 3)), so with NB = 2 (4) lane offsets, one per kk mod NB, every read is base + 64 kk
+    // fragment addressing (rs_frag_offsets written out: called from here it moves the register count of 28 instantiations, by up to + 27 — DESIGN.md)
     const int fsw = KS == 10 ? ((frow >> 1) & 7) : frow;      // swz() of this lane's fragment rows
     constexpr int NB = KS == 10 ? 2 : 4;
-    int foff[NB];
+    int foff[Cfg::NB];
 #pragma unroll
     for (int r = 0; r < NB; ++r) foff[r] = frow * RB + (fgrp ^ (fsw & 3)) * 16 + ((r ^ (fsw >> 2)) - r) * 64;
+    // (the residual variant at 64 rows per wave has no registers left for a second W fragment set: it is HBM-bound anyway)
+    constexpr int PFD = (RES && RT == 4) ? 0 : 1;      // W-fragment prefetch distance in k-steps
     auto mma_pair = [&](const unsigned char* sbase, const int q, f32x4_t (&c0)[RT], f32x4_t (&c1)[RT]) {
-        const unsigned char* tb[NB];
-#pragma unroll
-        for (int r = 0; r < NB; ++r) tb[r] = sbase + 32 * q * RB + foff[r];
-#pragma unroll
-        for (int i = 0; i < RT; ++i) { c0[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; c1[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-        // W fragments of k-step kk + PFD are requested before the MFMAs of k-step kk (the order is pinned: left alone the compiler
-        // issues each pair of reads right in front of its MFMAs and the matrix pipe waits out the LDS latency 10 times per pair;
-        // ablation on the GPU: with the reads removed the kernel runs 36-47 % faster, i.e. one k-step of cover — 8 MFMAs = 128
-        // cycles at 64 rows per wave, 64 cycles at 32 — is less than the loaded LDS latency)
-        // (the residual variant at 64 rows per wave has no registers left for a second fragment set: it is HBM-bound anyway)
-        constexpr int PFD = (RES && RT == 4) ? 0 : RS_PFD;
-        constexpr int NBUF = PFD + 1;
-        u32x4_t w0[NBUF], w1[NBUF];
-        auto rd = [&](const int kk, u32x4_t& x0, u32x4_t& x1) {
-            const unsigned char* t = tb[kk & (NB - 1)] + 64 * kk;
-            x0 = *reinterpret_cast<const u32x4_t*>(t);
-            x1 = *reinterpret_cast<const u32x4_t*>(t + 16 * RB);
-        };
-#pragma unroll
-        for (int kk = 0; kk < PFD; ++kk) rd(kk, w0[kk % NBUF], w1[kk % NBUF]);
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-            const int cur = kk % NBUF;
-            if (kk + PFD < KS) rd(kk + PFD, w0[(kk + PFD) % NBUF], w1[(kk + PFD) % NBUF]);
-            if constexpr (PFD > 0) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                c0[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w0[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c0[i], 0, 0, 0);
-                c1[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w1[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c1[i], 0, 0, 0);
-            }
-            if constexpr (PFD > 0) __builtin_amdgcn_sched_barrier(0);
-        }
+        rs_mma_pair<false, PFD, Cfg>(a, sbase, q, foff, c0, c1);
     };
     // residual of one pair in store layout, requested before the pair's MFMAs
     auto load_res = [&](const int ocol, u32x4_t (&rv)[RT]) {
@@ -285,30 +177,13 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
             rv[i] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, row_ok(i) ? rvo : OOB, (uint32_t)((m_wave + 16 * i) * p.ldr + ocol) * 2u, 0);
     };
     auto store_pair = [&](const int ocol, const int i, u32x4_t o) {
-        o = swap16_xz_yw(o);
-        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, row_ok(i) ? ovo : OOB, (uint32_t)((m_wave + 16 * i) * p.ldo + ocol) * 2u, 0);
-        // Store-data discipline (cf. gemm_glds_common.h): the allocator hands the store's registers to the next row tile's
-        // v_pk_add_f32 at once, and with the VALU write directly behind the store the LAST dword of the last four lanes of
-        // every 16-lane row went out holding the new fp32 value (first GPU run of this kernel: every launch, rows 12-15 of a
-        // tile, channels 6-7 of each 8).  The data stays live — and nothing is issued — for 8 states after the store.
-        asm volatile("s_nop 7" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w) : "memory");
+        rs_store16(rs_swap16(o), out_rsrc, row_ok(i) ? ovo : OOB, (uint32_t)((m_wave + 16 * i) * p.ldo + ocol) * 2u);
     };
 
     // body b: W rows [64 b, 64 b + 64) of the block = two pairs; one chunk (G = 4) or two (G = 2)
     const int nbody = ncols / 64;
     int c = 0, slot = 0;
-    auto chunk_end = [&](const int stores) {       // the wave's stores issued behind chunk c + 2's DMA (or a lower bound)
-        if (c + 1 < NC) {
-            // chunk c + 1 landed (mine): everything issued after its DMA — chunk c + 2's DMA and this chunk's stores — may stay in flight
-            wait_vmcnt_rt((c + 2 < NC ? P : 0) + stores);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();          // every wave is done with slot `slot`, chunk c + 1 is visible
-            asm volatile("" ::: "memory");
-            if (c + Cfg::STAGES < NC) issue_chunk(c + Cfg::STAGES, slot);
-        }
-        ++c;
-        slot = slot + 1 == Cfg::STAGES ? 0 : slot + 1;
-    };
+    auto chunk_end = [&](const int stores) { rs_ring_step<Cfg>(c, slot, NC, stores, issue_chunk); };
     for (int b = 0; b < nbody; ++b) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -333,10 +208,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
                     v.x *= gelu_erf_f(gt.x); v.y *= gelu_erf_f(gt.y); v.z *= gelu_erf_f(gt.z); v.w *= gelu_erf_f(gt.w);
                     hp[i].x = pack_elem2(v.x, v.y); hp[i].y = pack_elem2(v.z, v.w);
                     if (i & 1) {
-                        u32x4_t o = swap16_xz_yw(u32x4_t{hp[i - 1].x, hp[i - 1].y, hp[i].x, hp[i].y});
+                        const u32x4_t o = rs_swap16(u32x4_t{hp[i - 1].x, hp[i - 1].y, hp[i].x, hp[i].y});
                         const bool ok = m_wave + 16 * (i - 1 + (fgrp & 1)) + frow < p.M;
-                        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, ok ? ovo_g : OOB, (uint32_t)((m_wave + 16 * (i - 1)) * p.ldo + ocol) * 2u, 0);
-                        asm volatile("s_nop 7" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w) : "memory");       // (store-data discipline: store_pair)
+                        rs_store16(o, out_rsrc, ok ? ovo_g : OOB, (uint32_t)((m_wave + 16 * (i - 1)) * p.ldo + ocol) * 2u);
                     }
                     // one row tile at a time: left alone the scheduler interleaves all 16 GELUs of the pair for ILP
                     __builtin_amdgcn_sched_barrier(0);
@@ -346,7 +220,7 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
                 for (int i = 0; i < RT; ++i) {
                     f32x4_t v0 = c0[i] + b0, v1 = c1[i] + b1;
                     if constexpr (RES) {
-                        const u32x4_t r = swap16_xz_yw(rv[i]);   // store layout -> this lane's 4 channels of tile 2 q (x, y) and 2 q + 1 (z, w)
+                        const u32x4_t r = rs_swap16(rv[i]);   // store layout -> this lane's 4 channels of tile 2 q (x, y) and 2 q + 1 (z, w)
                         v0.x += rs * elem_lo(r.x); v0.y += rs * elem_hi(r.x); v0.z += rs * elem_lo(r.y); v0.w += rs * elem_hi(r.y);
                         v1.x += rs * elem_lo(r.z); v1.y += rs * elem_hi(r.z); v1.z += rs * elem_lo(r.w); v1.w += rs * elem_hi(r.w);
                     }
@@ -365,17 +239,6 @@ __global__ __launch_bounds__(512, 1) void gemm_rs_kernel(const VmvGemmParams p, 
 }
 
 struct RsPlan { int rt, nsplit, cols; };
-
-int ncu_whole_xcds() {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        if (n < 8) n = 8;
-        ncu = n & ~7;
-    }
-    return ncu;
-}
 
 // rows per wave (RT) and column splits: fewest rounds x block time over the CUs; ties go to the larger row tile (fewer W bytes
 // per MAC) and the smaller split
@@ -465,7 +328,7 @@ int vmv_gemm_rs_launch(const VmvGemmParams& p, int tile, hipStream_t st) {
     if (!vmv_gemm_rs_supported(p)) return VMV_GLDS_UNSUPPORTED;
     RsPlan pl;
     const int force_rt = tile == VMV_TILE_RS512 ? 4 : tile == VMV_TILE_RS256 ? 2 : 0;
-    if (!rs_plan(p, force_rt, pl, ncu_whole_xcds())) return VMV_GLDS_UNSUPPORTED;
+    if (!rs_plan(p, force_rt, pl, rs_ncu_whole_xcds())) return VMV_GLDS_UNSUPPORTED;
     const int mode = (p.epilogue == VMV_EPI_GEGLU ? RS_GEGLU : 0) | (p.colsum ? RS_LN : 0) | (p.residual ? RS_RES : 0) | (p.gn_table ? RS_GN : 0);
     if (p.ktot == 320) return pl.rt == 4 ? launch_rs_mode<4, 10>(p, pl, mode, st) : launch_rs_mode<2, 10>(p, pl, mode, st);
     if (p.ktot == 512) return launch_rs_mode<2, 16>(p, pl, mode, st);      // (the init TemporalTransformer: 8 heads x 64 on a 320-channel level)

@@ -6,8 +6,8 @@
 // Why.  In the two-kernel form the row-stationary GEMM writes q | k | v of every (frame, pixel) row — 236 MB at the first level of the
 // 24 x 40 x 64 plan — and attn_short_kernel reads them straight back to do 3.8 GFLOP on them at 45 TFLOP/s (81-84 us, HBM-bound); both
 // launches move 3-4 x the bytes of the activation they started from.  Here a wave keeps ALL F frames of 48 / F pixels — 48 rows = three
-// 16-row MFMA fragments, the whole K = 320 range — in registers (gemm_rs.hip's row-stationary scheme), streams the weight matrix
-// through the same three-stage LDS ring in head-major order [head][q | k | v][64 rows], and finishes a head's attention in registers
+// 16-row MFMA fragments, the whole K = 320 range — in registers (the row-stationary scheme of gemm_rs_common.h), streams the weight matrix
+// through its three-stage LDS ring in head-major order [head][q | k | v][64 rows], and finishes a head's attention in registers
 // before the next head's weights arrive: q, k and v never exist in memory, only the 64-column attention output of each head is stored.
 //
 // No lane ever needs another lane's data between the projection and the attention, because the contraction indices can be permuted:
@@ -19,11 +19,11 @@
 //     them transposes the result): lane (u, g) holds V[rows 4 g + r of fragment i][channel u] — which IS the A operand V^T[d = u][keys
 //     4 g + r] of a 16-deep MFMA whose B operand P^T[keys 4 g + r][query u] are the exponentiated S registers above:
 //         o[t] += MFMA16(A = v fragment (ik, tile t), B = p fragment ik)  ->  lane (u, g): O[query u][channels 16 t + 4 g + r],
-//     the layout gemm_rs.hip's store path (two v_permlane16_swap -> 16-byte stores) starts from.
+//     the layout rs_store16 (gemm_rs_common.h: two v_permlane16_swap -> 16-byte stores) starts from.
 // Rows of a wave: tile row tr = 16 i + u -> pixel tr / F, frame tr % F (F = 24: fragment 1 holds frames 16-23 of the first pixel and
 // 0-7 of the second; scores between different pixels are masked, tile pairs that share no pixel are skipped).
 // Per head and wave: 360 projection MFMAs + 14 (S) + 28 (P V; 16-deep) and ~250 VALU operations of softmax, no LDS traffic but W.
-#include "gemm_glds_common.h"
+#include "gemm_rs_common.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -31,17 +31,13 @@ using namespace vmvg;
 
 namespace {
 
-constexpr int TQ_RT = 3, TQ_KS = 10, TQ_K = 320;
-constexpr int TQ_NW = 8, TQ_NT = 512;
+using TqRing = RsRing<10>;                                  // chunk = 64 W rows of K = 320 = one of q / k / v of one head
+constexpr int TQ_RT = 3, TQ_KS = TqRing::KS, TQ_K = TqRing::K;
 constexpr int TQ_ROWS = 16 * TQ_RT;                         // tile rows of a wave (F x pixels)
-constexpr int TQ_RB = TQ_K * 2;                             // bytes per W row
-constexpr int TQ_SPR = TQ_RB / 16;                          // 16-byte slots per W row
-constexpr int TQ_CHUNK = 40960, TQ_CROWS = TQ_CHUNK / TQ_RB;      // a chunk = 64 W rows = one of k / v / q of one head
-constexpr int TQ_STAGES = 3;
-constexpr int TQ_P = TQ_CHUNK / 1024 / TQ_NW;               // LDS-DMA wave-instructions per wave per chunk (5)
+constexpr int TQ_CHUNK = TqRing::CHUNK_BYTES;
 constexpr int TQ_MAXCOLS = 3840;                            // 20 heads
-constexpr int TQ_LDS = TQ_STAGES * TQ_CHUNK + TQ_MAXCOLS * 4;
-static_assert(TQ_CROWS == 64 && TQ_P * TQ_NW * 1024 == TQ_CHUNK && TQ_LDS <= 160 * 1024, "chunk geometry");
+constexpr int TQ_LDS = TqRing::STAGES * TQ_CHUNK + TQ_MAXCOLS * 4;
+static_assert(TqRing::CROWS == 64 && TQ_LDS <= 160 * 1024, "chunk geometry");
 constexpr float TQ_NEG = -1.0e30f;
 
 #if defined(VMV_BUILD_BF16)
@@ -51,12 +47,6 @@ typedef __attribute__((ext_vector_type(4))) short tq_elem4_t;
 typedef __attribute__((ext_vector_type(4))) _Float16 tq_elem4_t;
 #define TQ_MFMA_K16 __builtin_amdgcn_mfma_f32_16x16x16f16
 #endif
-
-VMV_DEV u32x4_t tq_swap16(u32x4_t v) {          // gemm_rs.hip swap16_xz_yw (see there for the wait states)
-    uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-    asm("s_nop 3\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));
-    return u32x4_t{x, y, z, w};
-}
 
 // NEED: bit 3 iq + ik set = query fragment iq and key fragment ik share a pixel (compile-time: the unneeded score tiles, their P^T
 // registers and MFMAs do not exist).  F | 16: the diagonal; F = 24 / 12 / 6 / 3: the band; F = 48: all nine.
@@ -76,7 +66,7 @@ static_assert(TQ_DIAG == 0x111u && TQ_BAND == 0x1bbu && TQ_FULL == 0x1ffu && tq_
 template <bool LN, uint32_t NEED>
 __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p, const int ntiles, const int heads, const int npix) {
     VMV_KERNEL_ENTER();
-    constexpr int RT = TQ_RT, KS = TQ_KS, RB = TQ_RB, P = TQ_P;
+    constexpr int RT = TQ_RT, KS = TQ_KS, P = TqRing::PIECES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -103,88 +93,37 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
     int qlo[RT];                                                // first tile row of the pixel that owns tile row 16 i + frow
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(sg.src), 0, (uint32_t)p.M * (uint32_t)sg.ld * 2u, SRD_FLAGS);
     u32x4_t a[RT][KS];
-    auto load_tile = [&](const int tile) __attribute__((always_inline)) {                      // the rows of row tile `tile` into the registers (rows outside the tensor: zeros)
-        const int gp0 = (tile * TQ_NW + wave) * PPW;            // first (sample, pixel) index of this wave
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const int tr = 16 * i + frow;
-            const int px = tr / F, f = tr - px * F;
-            const int gp = gp0 + px;
-            const bool ok = gp < npix;
-            const int b = gp / PX, pp = gp - b * PX;
-            const long m = ((long)b * F + f) * PX + pp;
-            const uint32_t avo = ok ? (uint32_t)((m * sg.ld + 8 * fgrp) * 2) : OOB;
-            ovo[i] = ok ? (uint32_t)((m * p.ldo + lanecol) * 2) : OOB;
-            qlo[i] = px * F;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) a[i][kk] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, avo + (uint32_t)(kk * 64), 0, 0);
-        }
+    auto load_tile = [&](const int tile) __attribute__((always_inline)) {                      // pixel-major rows of row tile `tile`
+        const int gp0 = (tile * TqRing::NW + wave) * PPW;          // first (sample, pixel) index of this wave
+        rs_load_rows(a, a_rsrc, sg.ld, gp0, frow, fgrp, F, PX, npix, [&](const int tr, int& f, int& px) { px = tr / F; f = tr - px * F; },
+                     [&](const int i, const bool ok, const int, const long m, const int px) {
+                         ovo[i] = ok ? (uint32_t)((m * p.ldo + lanecol) * 2) : OOB;
+                         qlo[i] = px * F;
+                     });
     };
     int cur_tile = i0 / heads;
     load_tile(cur_tile);
 
-    // ---- bias strip (the folded LayerNorm's W beta, head-major like W), then the W ring (gemm_rs.hip: swizzle (r >> 1) & 7 on the SOURCE)
-    float* bias_lds = reinterpret_cast<float*>(smem + TQ_STAGES * TQ_CHUNK);
+    // ---- bias strip (the folded LayerNorm's W beta, head-major like W), then the W ring
+    float* bias_lds = reinterpret_cast<float*>(smem + TqRing::STAGES * TQ_CHUNK);
     {
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (uint32_t)p.N * 4u : 0u, SRD_FLAGS);
-        for (int q = wave; q * 256 < p.N; q += TQ_NW)
+        for (int q = wave; q * 256 < p.N; q += TqRing::NW)
             blds16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
     }
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     auto issue_chunk = [&](int c, int slot) {
-        unsigned char* base = smem + slot * TQ_CHUNK + wave * (P * 1024);
+        unsigned char* base = TqRing::wave_base(smem + slot * TQ_CHUNK, wave);
         const int it = c / 3, hc = (i0 + it) % heads;          // chunk c = section c % 3 of the head of item i0 + c / 3
-        const uint32_t so = (uint32_t)((3 * hc + (c - 3 * it)) * TQ_CROWS * p.ktot) * 2u;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));                           // (recomputed per chunk instead of five more live registers: gemm_rs.hip)
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int u = wave * (P * 64) + q * 64 + ln;
-            const int r = u / TQ_SPR, s = u - r * TQ_SPR;
-            const int sw = (r >> 1) & 7;
-            blds16(w_rsrc, base + q * 1024, (uint32_t)(r * p.ktot + (s ^ sw) * 8) * 2u, so);
-        }
+        const uint32_t so = (uint32_t)((3 * hc + (c - 3 * it)) * TqRing::CROWS * p.ktot) * 2u;
+        rs_issue_rows<TqRing>(w_rsrc, base, wave, lane, so, [&](const int r) { return r * p.ktot; });
     };
     const int NC = 3 * nit;
-    for (int c = 0; c < TQ_STAGES; ++c) issue_chunk(c, c);       // (NC >= 3 always)
+    for (int c = 0; c < TqRing::STAGES; ++c) issue_chunk(c, c);       // (NC >= 3 always)
 
-    // ---- LayerNorm of the resident rows (two-pass, fp32; gemm_rs.hip): the plain product with W' = W diag(gamma) follows
+    // ---- LayerNorm of the resident rows: the plain product with W' = W diag(gamma) follows
     auto layernorm_rows = [&]() __attribute__((always_inline)) {        // (called twice: out of line the rows would live in scratch)
-    if constexpr (LN) {
-        const float inv_k = 1.0f / (float)TQ_K;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            float s1 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                elem_dot2c(s1, a[i][kk].x, VMV_ELEM_ONE2); elem_dot2c(s1, a[i][kk].y, VMV_ELEM_ONE2);
-                elem_dot2c(s1, a[i][kk].z, VMV_ELEM_ONE2); elem_dot2c(s1, a[i][kk].w, VMV_ELEM_ONE2);
-            }
-            asm volatile("s_nop 4" : "+v"(s1));                // (DOT-pipe result -> VALU read: gemm_rs.hip)
-            const float mean = xor16_32_sum(s1) * inv_k;
-            float s2 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const uint32_t w4[4] = {a[i][kk].x, a[i][kk].y, a[i][kk].z, a[i][kk].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d0 = elem_lo(w4[e]) - mean, d1 = elem_hi(w4[e]) - mean;
-                    s2 = fmaf(d0, d0, s2); s2 = fmaf(d1, d1, s2);
-                }
-            }
-            const float rstd = __builtin_amdgcn_rsqf(xor16_32_sum(s2) * inv_k + p.ln_eps);
-            const float nm = -mean * rstd;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) asm volatile("" : "+v"(a[i][kk].x), "+v"(a[i][kk].y), "+v"(a[i][kk].z), "+v"(a[i][kk].w));
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                a[i][kk].x = pack_elem2(fmaf(elem_lo(a[i][kk].x), rstd, nm), fmaf(elem_hi(a[i][kk].x), rstd, nm));
-                a[i][kk].y = pack_elem2(fmaf(elem_lo(a[i][kk].y), rstd, nm), fmaf(elem_hi(a[i][kk].y), rstd, nm));
-                a[i][kk].z = pack_elem2(fmaf(elem_lo(a[i][kk].z), rstd, nm), fmaf(elem_hi(a[i][kk].z), rstd, nm));
-                a[i][kk].w = pack_elem2(fmaf(elem_lo(a[i][kk].w), rstd, nm), fmaf(elem_hi(a[i][kk].w), rstd, nm));
-            }
-        }
-    }
+        if constexpr (LN) rs_layernorm_rows(a, p.ln_eps);
     };
     layernorm_rows();
 
@@ -198,43 +137,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    const int fsw = (frow >> 1) & 7;
-    int foff[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) foff[r] = frow * RB + (fgrp ^ (fsw & 3)) * 16 + ((r ^ (fsw >> 2)) - r) * 64;
-    // one pair of 16-row W tiles against the resident rows.  SWAP = false: transposed product (c: row frow, channels 4 fgrp + r of the
-    // tile); SWAP = true: plain product (c: rows 4 fgrp + r, channel frow of the tile).  W fragments one k-step ahead (gemm_rs.hip).
+    int foff[TqRing::NB];
+    rs_frag_offsets<TqRing>(frow, fgrp, foff);
+    // one pair of 16-row W tiles against the resident rows, transposed (q, k) or plain (v: swap_tag true) product
     auto mma_pair = [&](const unsigned char* sbase, const int q, f32x4_t (&c0)[RT], f32x4_t (&c1)[RT], auto swap_tag) {
-        constexpr bool SWAP = decltype(swap_tag)::value;
-        const unsigned char* tb[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) tb[r] = sbase + 32 * q * RB + foff[r];
-#pragma unroll
-        for (int i = 0; i < RT; ++i) { c0[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; c1[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-        u32x4_t w0[2], w1[2];
-        auto rd = [&](const int kk, u32x4_t& x0, u32x4_t& x1) {
-            const unsigned char* t = tb[kk & 1] + 64 * kk;
-            x0 = *reinterpret_cast<const u32x4_t*>(t);
-            x1 = *reinterpret_cast<const u32x4_t*>(t + 16 * RB);
-        };
-        rd(0, w0[0], w1[0]);
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-            const int cur = kk & 1;
-            if (kk + 1 < KS) rd(kk + 1, w0[cur ^ 1], w1[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                if constexpr (SWAP) {
-                    c0[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, a[i][kk]), __builtin_bit_cast(elem8_t, w0[cur]), c0[i], 0, 0, 0);
-                    c1[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, a[i][kk]), __builtin_bit_cast(elem8_t, w1[cur]), c1[i], 0, 0, 0);
-                } else {
-                    c0[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w0[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c0[i], 0, 0, 0);
-                    c1[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w1[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c1[i], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        rs_mma_pair<decltype(swap_tag)::value, 1, TqRing>(a, sbase, q, foff, c0, c1);
     };
     using T_ = std::integral_constant<bool, true>;
     using F_ = std::integral_constant<bool, false>;
@@ -242,17 +149,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
     int c = 0, slot = 0;
     // chunk c consumed: chunk c + 1 landed for every wave, slot of chunk c refilled with chunk c + 3.  `extra` = this wave's stores that
     // were issued behind chunk c + 1's DMA (the previous and the current chunk's): they and chunk c + 2's DMA may stay in flight.
-    auto chunk_end = [&](const int extra) {
-        if (c + 1 < NC) {
-            wait_vmcnt_rt((c + 2 < NC ? P : 0) + extra);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (c + TQ_STAGES < NC) issue_chunk(c + TQ_STAGES, slot);
-        }
-        ++c;
-        slot = slot + 1 == TQ_STAGES ? 0 : slot + 1;
-    };
+    auto chunk_end = [&](const int extra) { rs_ring_step<TqRing>(c, slot, NC, extra, issue_chunk); };
     // a fragment of 8 (k, q) or 4 (v) 16-bit values from fp32 accumulators
     auto pack_kq = [&](const f32x4_t& v0, const f32x4_t& v1) {
         return u32x4_t{pack_elem2(v0.x, v0.y), pack_elem2(v0.z, v0.w), pack_elem2(v1.x, v1.y), pack_elem2(v1.z, v1.w)};
@@ -358,27 +255,13 @@ __global__ __launch_bounds__(512, 1) void gemm_tqa_kernel(const VmvGemmParams p,
                         }
                     }
                     o0 *= linv[iq]; o1 *= linv[iq];
-                    u32x4_t ov = tq_swap16(pack_kq(o0, o1));
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, out_rsrc, ovo[iq], (uint32_t)(64 * h + 32 * pr) * 2u, 0);
-                    asm volatile("s_nop 7" ::"v"(ov.x), "v"(ov.y), "v"(ov.z), "v"(ov.w) : "memory");       // (store-data discipline: gemm_rs.hip)
+                    rs_store16(rs_swap16(pack_kq(o0, o1)), out_rsrc, ovo[iq], (uint32_t)(64 * h + 32 * pr) * 2u);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             chunk_end(2 * RT);
         }
     }
-}
-
-int tqa_ncu() {          // CUs of whole XCDs (one block per CU; gemm_rs.hip ncu_whole_xcds)
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (vmv_dry_run || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        if (n < 8) n = 8;
-        if (vmv_dry_run) return n & ~7;      // (validation without a device must not cache the guess)
-        ncu = n & ~7;
-    }
-    return ncu;
 }
 
 }  // namespace
@@ -402,28 +285,24 @@ bool vmv_gemm_tqa_supported(const VmvGemmParams& p) {
 // 24 x 40 x 64, 46 against 71 at 24 x 32 x 32, 24 against 54 on rank 0 of 8 (40 row tiles x 5 heads = 200 items).
 bool vmv_gemm_tqa_preferred(const VmvGemmParams& p) {
     if (!vmv_gemm_tqa_supported(p)) return false;
-    const long npix = (long)(p.M / ((long)p.F * p.P)) * p.P;
-    const long tiles = (npix + TQ_NW * (TQ_ROWS / p.F) - 1) / (TQ_NW * (TQ_ROWS / p.F));
     static long min_items = -1;
     if (min_items < 0) { const char* e = getenv("VMV_TQA_MIN_ITEMS"); min_items = e ? atol(e) : 128; }      // (tests reach the kernel at small shapes)
-    return tiles * (p.N / 192) >= min_items;
+    return (long)rs_pixel_tiles(p, TQ_ROWS).ntiles * (p.N / 192) >= min_items;
 }
 
 int vmv_gemm_tqa_launch(const VmvGemmParams& p, hipStream_t st) {
     if (!vmv_gemm_tqa_supported(p)) return VMV_GLDS_UNSUPPORTED;
-    const int npix = (int)((p.M / ((long)p.F * p.P)) * p.P);
-    const int ppb = TQ_NW * (TQ_ROWS / p.F);
-    const int ntiles = (npix + ppb - 1) / ppb;
+    const int npix = rs_pixel_tiles(p, TQ_ROWS).npix, ntiles = rs_pixel_tiles(p, TQ_ROWS).ntiles;
     const int heads = p.N / 192;
     const long nitems = (long)ntiles * heads;
-    const int nblk = (int)(nitems < tqa_ncu() ? nitems : tqa_ncu());
+    const int nblk = (int)(nitems < rs_ncu_whole_xcds() ? nitems : rs_ncu_whole_xcds());
     const uint32_t need = tq_need_mask(p.F);
     const bool ln = p.colsum != nullptr;
 #define TQ_LAUNCH(LNV, NEEDV)                                                                                                            \
     do {                                                                                                                                 \
         static std::atomic<unsigned long long> attr{0};                                                                                  \
         if (const int rc = vmv_lds_attr_once(attr, reinterpret_cast<const void*>(&gemm_tqa_kernel<LNV, NEEDV>), TQ_LDS)) return rc;      \
-        VMV_LAUNCH((gemm_tqa_kernel<LNV, NEEDV>), dim3(nblk), dim3(TQ_NT), TQ_LDS, st, p, ntiles, heads, npix);                          \
+        VMV_LAUNCH((gemm_tqa_kernel<LNV, NEEDV>), dim3(nblk), dim3(TqRing::NT), TQ_LDS, st, p, ntiles, heads, npix);                          \
     } while (0)
     if (need == TQ_BAND) { if (ln) TQ_LAUNCH(true, TQ_BAND); else TQ_LAUNCH(false, TQ_BAND); }
     else if (need == TQ_DIAG) { if (ln) TQ_LAUNCH(true, TQ_DIAG); else TQ_LAUNCH(false, TQ_DIAG); }

@@ -12,18 +12,18 @@
 //   * A wave owns 48 rows = all F frames of PPW = 48 / F pixels, FRAME-major: tile row tr = 16 i + u -> frame tr / PPW, pixel
 //     tr % PPW.  A frame step is then a uniform shift by PPW rows, and the missing tap of the first / last frame is the shift's own
 //     zero fill.  Rows of pixels past the tensor are read as zeros and never stored; a shift never mixes pixels (tr % PPW is kept).
-//   * The rows are loaded once per row tile straight into registers (gemm_tqa.hip) and — folded form — normalised there:
+//   * The rows are loaded once per row tile straight into registers (rs_load_rows) and — folded form — normalised there:
 //     elem(silu(x * scale + shift)) in fp32, the values vmv_groupnorm_apply stores, with each row's own sample's table row (the
 //     tables of all samples, <= 8, sit in LDS behind the bias strip).
-//   * W streams through gemm_rs.hip's three-stage ring of 64-row chunks by LDS-DMA; the DMA's source address orders the rows of a
+//   * W streams through the three-stage ring of 64-row chunks of gemm_rs_common.h by LDS-DMA; the DMA's source address orders the rows of a
 //     64-channel group as (pair 0: tap 0, 1, 2), (pair 1: tap 0, 1, 2), 32 rows each — six halves = three chunks per item.
 //   * Per 32-column pair: tap 0's product is shifted down by PPW rows into the output registers, tap 1's is added, tap 2's is shifted
 //     up and added.  In the transposed-product layout a row is lane u of fragment i of a 16-lane group, so the shift is a DPP
 //     row_shr / row_shl plus the carry from the neighbouring fragment (row_ror into the lanes the shift leaves): no LDS, no barrier.
-//     Then bias, residual, v_permlane16_swap and 16-byte stores as in gemm_rs.hip.
+//     Then bias, residual, v_permlane16_swap and 16-byte stores (rs_swap16 / rs_store16).
 //   * Persistent blocks, one per CU, over contiguous, equally long ranges of (row tile, 64-channel group) items (gemm_tqa.hip); the
 //     rows are re-loaded (and re-normalised) only where a range crosses a row-tile boundary.
-#include "gemm_glds_common.h"
+#include "gemm_rs_common.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -33,26 +33,16 @@ bool vmv_gemm_tfr_preferred(const VmvGemmParams& p);            // gemm_tfr.hip
 
 namespace {
 
-constexpr int TR_RT = 3, TR_KS = 10, TR_K = 320;
-constexpr int TR_NW = 8, TR_NT = 512;
+using TrRing = RsRing<10>;                                  // chunk = 64 W rows of K = 320 = two (pair, tap) halves
+constexpr int TR_RT = 3, TR_KS = TrRing::KS, TR_K = TrRing::K;
 constexpr int TR_ROWS = 16 * TR_RT;                         // tile rows of a wave (F x pixels)
-constexpr int TR_RB = TR_K * 2;                             // bytes per W row
-constexpr int TR_SPR = TR_RB / 16;                          // 16-byte slots per W row
-constexpr int TR_CHUNK = 40960, TR_CROWS = TR_CHUNK / TR_RB;      // a chunk = 64 W rows = two (pair, tap) halves
-constexpr int TR_STAGES = 3;
-constexpr int TR_P = TR_CHUNK / 1024 / TR_NW;               // LDS-DMA wave-instructions per wave per chunk (5)
+constexpr int TR_RB = TrRing::RB, TR_CHUNK = TrRing::CHUNK_BYTES, TR_STAGES = TrRing::STAGES;
 constexpr int TR_MAXCOLS = 1280;                            // bias strip
 constexpr int TR_MAXSAMP = 8;                               // samples whose norm tables fit behind it
 constexpr int TR_TAB = TR_MAXSAMP * 2 * TR_K * 4;           // [sample][scale | shift][C] fp32: 20 KB (whole 1-KB DMA pieces)
 constexpr int TR_OFF_BIAS = TR_STAGES * TR_CHUNK, TR_OFF_TAB = TR_OFF_BIAS + TR_MAXCOLS * 4;
 constexpr int TR_LDS = TR_OFF_TAB + TR_TAB;
-static_assert(TR_CROWS == 64 && TR_P * TR_NW * 1024 == TR_CHUNK && (TR_TAB % 1024) == 0 && TR_LDS <= 160 * 1024, "chunk geometry");
-
-VMV_DEV u32x4_t tr_swap16(u32x4_t v) {          // gemm_rs.hip swap16_xz_yw (see there for the wait states)
-    uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-    asm("s_nop 3\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));
-    return u32x4_t{x, y, z, w};
-}
+static_assert(TrRing::CROWS == 64 && (TR_TAB % 1024) == 0 && TR_LDS <= 160 * 1024, "chunk geometry");
 
 // DPP move inside the 16-lane rows: a lane whose source lane lies outside its row keeps `old`
 constexpr int DPP_ROW_SHL = 0x100, DPP_ROW_SHR = 0x110, DPP_ROW_ROR = 0x120;
@@ -92,7 +82,7 @@ VMV_DEV void tr_shift_up_add(const f32x4_t (&y)[TR_RT], f32x4_t (&o)[TR_RT]) {
 template <bool GN, bool RES, int S>
 __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p, const int ntiles, const int ngroups, const int npix) {
     VMV_KERNEL_ENTER();
-    constexpr int RT = TR_RT, KS = TR_KS, RB = TR_RB, P = TR_P, PPW = S, F = TR_ROWS / S;
+    constexpr int RT = TR_RT, KS = TR_KS, RB = TR_RB, P = TrRing::PIECES, PPW = S, F = TR_ROWS / S;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -114,69 +104,55 @@ __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p,
     uint32_t tabo[RT];
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(sg.src), 0, (uint32_t)p.M * (uint32_t)sg.ld * 2u, SRD_FLAGS);
     u32x4_t a[RT][KS];
-    auto load_tile = [&](const int tile) __attribute__((always_inline)) {      // the rows of row tile `tile` into the registers (rows outside the tensor: zeros)
-        const int gp0 = (tile * TR_NW + wave) * PPW;            // first (sample, pixel) index of this wave
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const int tr = 16 * i + frow;
-            const int f = tr / PPW, px = tr - f * PPW;
-            const int gp = gp0 + px;
-            const bool ok = gp < npix;
-            const int b = gp / PX, pp = gp - b * PX;
-            const long m = ((long)b * F + f) * PX + pp;
-            const uint32_t avo = ok ? (uint32_t)((m * sg.ld + 8 * fgrp) * 2) : OOB;
-            mrow[i] = ok ? (int)m : -1;
-            tabo[i] = (uint32_t)(TR_OFF_TAB + ((ok ? b : 0) * 2 * TR_K + 8 * fgrp) * 4);      // this row's sample's table, this lane's k-slice
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) a[i][kk] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, avo + (uint32_t)(kk * 64), 0, 0);
-        }
+    auto load_tile = [&](const int tile) __attribute__((always_inline)) {      // frame-major rows of row tile `tile`
+        const int gp0 = (tile * TrRing::NW + wave) * PPW;          // first (sample, pixel) index of this wave
+        rs_load_rows(a, a_rsrc, sg.ld, gp0, frow, fgrp, F, PX, npix, [&](const int tr, int& f, int& px) { f = tr / PPW; px = tr - f * PPW; },
+                     [&](const int i, const bool ok, const int b, const long m, const int) {
+                         mrow[i] = ok ? (int)m : -1;
+                         tabo[i] = (uint32_t)(TR_OFF_TAB + ((ok ? b : 0) * 2 * TR_K + 8 * fgrp) * 4);      // this row's sample's table, this lane's k-slice
+                     });
     };
     int cur_tile = i0 / ngroups;
     load_tile(cur_tile);
 
-    // ---- bias strip, the norm tables of every sample, then the W ring (gemm_rs.hip: swizzle (r >> 1) & 7 on the SOURCE)
+    // ---- bias strip, the norm tables of every sample, then the W ring
     float* bias_lds = reinterpret_cast<float*>(smem + TR_OFF_BIAS);
     {
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, p.bias ? (uint32_t)p.N * 4u : 0u, SRD_FLAGS);
-        for (int q = wave; q * 256 < TR_MAXCOLS; q += TR_NW)    // (columns >= N / no bias: zeros)
+        for (int q = wave; q * 256 < TR_MAXCOLS; q += TrRing::NW)    // (columns >= N / no bias: zeros)
             blds16(b_rsrc, reinterpret_cast<unsigned char*>(bias_lds) + q * 1024, (uint32_t)(q * 256 + 4 * lane) * 4u, 0);
     }
     if constexpr (GN) {
         const uint32_t tbytes = (uint32_t)(p.M / (F * PX)) * (uint32_t)(2 * TR_K * 4);      // <= TR_TAB (launcher)
         const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gn_table), 0, tbytes, SRD_FLAGS);
-        for (int q = wave; q * 1024 < (int)tbytes; q += TR_NW)
+        for (int q = wave; q * 1024 < (int)tbytes; q += TrRing::NW)
             blds16(t_rsrc, smem + TR_OFF_TAB + q * 1024, (uint32_t)(q * 1024 + 16 * lane), 0);
     }
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (uint32_t)p.N * (uint32_t)p.ktot * 2u, SRD_FLAGS);
     // chunk c of the block = halves 2 cc, 2 cc + 1 (cc = c % 3) of item i0 + c / 3; half hh = (pair hh / 3, tap hh % 3): chunk row r
     // is W row (n0 + 32 pair + (r & 31), tap) — channels >= N read as zeros through the descriptor
     auto issue_chunk = [&](int c, int slot) {
-        unsigned char* base = smem + slot * TR_CHUNK + wave * (P * 1024);
+        unsigned char* base = TrRing::wave_base(smem + slot * TR_CHUNK, wave);
         const int it = c / 3, cc = c - 3 * it;
         const int n0 = 64 * ((i0 + it) % ngroups);
-        int ln = lane;
-        asm volatile("" : "+v"(ln));                           // (recomputed per chunk instead of five more live registers: gemm_rs.hip)
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int u = wave * (P * 64) + q * 64 + ln;
-            const int r = u / TR_SPR, s = u - r * TR_SPR;
-            const int sw = (r >> 1) & 7;
+        rs_issue_rows<TrRing>(w_rsrc, base, wave, lane, 0, [&](const int r) {
             const int hh = 2 * cc + (r >> 5);
             const int pr = hh >= 3 ? 1 : 0, tp = hh - 3 * pr;
             const int n = n0 + 32 * pr + (r & 31);
-            blds16(w_rsrc, base + q * 1024, (uint32_t)(n * p.ktot + tp * TR_K + (s ^ sw) * 8) * 2u, 0);
-        }
+            return n * p.ktot + tp * TR_K;
+        });
     };
     const int NC = 3 * nit;
     for (int c = 0; c < TR_STAGES; ++c) issue_chunk(c, c);       // (NC >= 3 always)
 
     // ---- folded GroupNorm (+ SiLU) on the resident rows: x <- elem(silu(x * scale[c] + shift[c])), the values vmv_groupnorm_apply
-    //      would have stored.  The loop is fenced per (row fragment, k-step) and reads one step ahead (gemm_rs.hip RS_GN).
+    //      would have stored.  The loop is fenced per (row fragment, k-step) and reads one step ahead: left to itself the scheduler hoists
+    //      every step's reads (600 spilled registers).  (gemm_rs.hip's proj_in fold is the same loop without SiLU, packing per dword.)
     const bool silu = p.gn_silu != 0;
     auto fold_rows = [&]() __attribute__((always_inline)) {
         if constexpr (GN) {
             f32x4_t tv[2][4];
-            int chain = 0;                               // always 0; ties each read to an earlier step's result
+            int chain = 0;                               // always 0; ties each read to an earlier step's result (the asm below)
             auto rd = [&](int idx, f32x4_t (&t)[4]) {
                 const float* tb = reinterpret_cast<const float*>(smem + tabo[idx / KS]) + (idx % KS) * 32 + chain;
                 t[0] = *reinterpret_cast<const f32x4_t*>(tb); t[1] = *reinterpret_cast<const f32x4_t*>(tb + 4);
@@ -199,6 +175,8 @@ __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p,
                 }
                 v.x = pack_elem2(x0, x1); v.y = pack_elem2(x2, x3); v.z = pack_elem2(x4, x5); v.w = pack_elem2(x6, x7);
                 a[idx / KS][idx % KS] = v;
+                // (a fence for the optimiser, not only the scheduler: without a data dependency every step's table reads are issued up
+                //  front — 640 live registers; the empty asm makes a later read's address "depend" on this step's result)
                 asm volatile("" : "+v"(chain) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -219,54 +197,22 @@ __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p,
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
+    // (rs_frag_offsets written out: called from here it costs 16 of the 24 instantiations 2-6 registers — DESIGN.md)
     const int fsw = (frow >> 1) & 7;
     int foff[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) foff[r] = frow * RB + (fgrp ^ (fsw & 3)) * 16 + ((r ^ (fsw >> 2)) - r) * 64;
     // one half = two 16-row W tiles (one tap of a 32-channel pair) against the resident rows, transposed product (c: row frow, channels
-    // 4 fgrp + r of the tile).  W fragments one k-step ahead (gemm_rs.hip).
+    // 4 fgrp + r of the tile)
     auto mma_pair = [&](const unsigned char* sbase, const int q, f32x4_t (&c0)[RT], f32x4_t (&c1)[RT]) {
-        const unsigned char* tb[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) tb[r] = sbase + 32 * q * RB + foff[r];
-#pragma unroll
-        for (int i = 0; i < RT; ++i) { c0[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; c1[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-        u32x4_t w0[2], w1[2];
-        auto rd = [&](const int kk, u32x4_t& x0, u32x4_t& x1) {
-            const unsigned char* t = tb[kk & 1] + 64 * kk;
-            x0 = *reinterpret_cast<const u32x4_t*>(t);
-            x1 = *reinterpret_cast<const u32x4_t*>(t + 16 * RB);
-        };
-        rd(0, w0[0], w1[0]);
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-            const int cur = kk & 1;
-            if (kk + 1 < KS) rd(kk + 1, w0[cur ^ 1], w1[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                c0[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w0[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c0[i], 0, 0, 0);
-                c1[i] = VMV_MFMA16(__builtin_bit_cast(elem8_t, w1[cur]), __builtin_bit_cast(elem8_t, a[i][kk]), c1[i], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        rs_mma_pair<false, 1, TrRing>(a, sbase, q, foff, c0, c1);
     };
 
     int c = 0, slot = 0;
     // chunk c consumed: chunk c + 1 landed for every wave, slot of chunk c refilled with chunk c + 3.  `extra` = a lower bound of this
     // wave's stores / residual loads issued behind chunk c + 1's DMA (the previous and the current chunk's): they and chunk c + 2's DMA
     // may stay in flight.
-    auto chunk_end = [&](const int extra) {
-        if (c + 1 < NC) {
-            wait_vmcnt_rt((c + 2 < NC ? P : 0) + extra);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (c + TR_STAGES < NC) issue_chunk(c + TR_STAGES, slot);
-        }
-        ++c;
-        slot = slot + 1 == TR_STAGES ? 0 : slot + 1;
-    };
+    auto chunk_end = [&](const int extra) { rs_ring_step<TrRing>(c, slot, NC, extra, issue_chunk); };
     // vector-memory operations of this wave per chunk of an item: chunk 0 none; chunk 1 the residual loads and stores of pair 0; chunk 2
     // those of pair 1
     constexpr int NVM = RES ? 2 * RT : RT;
@@ -309,14 +255,12 @@ __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p,
                     f32x4_t v0 = o0[i] + b0, v1 = o1[i] + b1;
                     act_apply(v0, p.act); act_apply(v1, p.act);
                     if constexpr (RES) {
-                        const u32x4_t r = tr_swap16(rv[i]);     // store layout -> this lane's 4 channels of the two tiles
+                        const u32x4_t r = rs_swap16(rv[i]);     // store layout -> this lane's 4 channels of the two tiles
                         v0.x += rs * elem_lo(r.x); v0.y += rs * elem_hi(r.x); v0.z += rs * elem_lo(r.y); v0.w += rs * elem_hi(r.y);
                         v1.x += rs * elem_lo(r.z); v1.y += rs * elem_hi(r.z); v1.z += rs * elem_lo(r.w); v1.w += rs * elem_hi(r.w);
                     }
-                    u32x4_t ov = u32x4_t{pack_elem2(v0.x, v0.y), pack_elem2(v0.z, v0.w), pack_elem2(v1.x, v1.y), pack_elem2(v1.z, v1.w)};
-                    ov = tr_swap16(ov);
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, out_rsrc, col_ok && mrow[i] >= 0 ? (uint32_t)(mrow[i] * p.ldo + lanecol) * 2u : OOB, (uint32_t)ocol * 2u, 0);
-                    asm volatile("s_nop 7" ::"v"(ov.x), "v"(ov.y), "v"(ov.z), "v"(ov.w) : "memory");       // (store-data discipline: gemm_rs.hip)
+                    const u32x4_t ov = u32x4_t{pack_elem2(v0.x, v0.y), pack_elem2(v0.z, v0.w), pack_elem2(v1.x, v1.y), pack_elem2(v1.z, v1.w)};
+                    rs_store16(rs_swap16(ov), out_rsrc, col_ok && mrow[i] >= 0 ? (uint32_t)(mrow[i] * p.ldo + lanecol) * 2u : OOB, (uint32_t)ocol * 2u);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -327,22 +271,8 @@ __global__ __launch_bounds__(512, 1) void gemm_trs_kernel(const VmvGemmParams p,
     }
 }
 
-int trs_ncu() {          // CUs of whole XCDs (one block per CU; gemm_tqa.hip)
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (vmv_dry_run || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        if (n < 8) n = 8;
-        if (vmv_dry_run) return n & ~7;      // (validation without a device must not cache the guess)
-        ncu = n & ~7;
-    }
-    return ncu;
-}
-
 long trs_items(const VmvGemmParams& p) {
-    const long npix = (long)(p.M / ((long)p.F * p.P)) * p.P;
-    const int ppb = TR_NW * (TR_ROWS / p.F);
-    return ((npix + ppb - 1) / ppb) * ((p.N + 63) / 64);
+    return (long)rs_pixel_tiles(p, TR_ROWS).ntiles * ((p.N + 63) / 64);
 }
 
 }  // namespace
@@ -377,19 +307,17 @@ bool vmv_gemm_trs_preferred(const VmvGemmParams& p) {
 // max_blocks > 0 caps the grid (tests: item ranges that cross row tiles at small shapes)
 int vmv_gemm_trs_launch(const VmvGemmParams& p, int max_blocks, hipStream_t st) {
     if (!vmv_gemm_trs_supported(p)) return VMV_GLDS_UNSUPPORTED;
-    const int npix = (int)((p.M / ((long)p.F * p.P)) * p.P);
-    const int ppb = TR_NW * (TR_ROWS / p.F);
-    const int ntiles = (npix + ppb - 1) / ppb;
+    const int npix = rs_pixel_tiles(p, TR_ROWS).npix, ntiles = rs_pixel_tiles(p, TR_ROWS).ntiles;
     const int ngroups = (p.N + 63) / 64;
-    const long nitems = (long)ntiles * ngroups;
-    int nblk = (int)(nitems < trs_ncu() ? nitems : trs_ncu());
+    const long nitems = trs_items(p);
+    int nblk = (int)(nitems < rs_ncu_whole_xcds() ? nitems : rs_ncu_whole_xcds());
     if (max_blocks > 0 && nblk > max_blocks) nblk = max_blocks;
     const bool gn = p.gn_table != nullptr, res = p.residual != nullptr;
 #define TR_LAUNCH1(GNV, RESV, SV)                                                                                                               \
     do {                                                                                                                                 \
         static std::atomic<unsigned long long> attr{0};                                                                                  \
         if (const int rc = vmv_lds_attr_once(attr, reinterpret_cast<const void*>(&gemm_trs_kernel<GNV, RESV, SV>), TR_LDS)) return rc;         \
-        VMV_LAUNCH((gemm_trs_kernel<GNV, RESV, SV>), dim3(nblk), dim3(TR_NT), TR_LDS, st, p, ntiles, ngroups, npix);                           \
+        VMV_LAUNCH((gemm_trs_kernel<GNV, RESV, SV>), dim3(nblk), dim3(TrRing::NT), TR_LDS, st, p, ntiles, ngroups, npix);                           \
     } while (0)
 #define TR_LAUNCH(SV)                                                                                                                    \
     do {                                                                                                                                 \
