@@ -45,7 +45,7 @@ int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
  * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams, 107 = VmvGsSsimLossParams,
- * 108 = VmvGsDepthParams */
+ * 108 = VmvGsDepthParams, 109 = VmvGsTsdfParams */
 int vmv_sizeof(int which);
 /* human-readable text for a code returned by any launcher (VMV_E* or hipError_t) */
 const char* vmv_error_string(int code);
@@ -662,6 +662,39 @@ typedef struct {
 } VmvGsSsimLossParams;
 int vmv_gs_ssim_loss_workspace_bytes(int planes, int height, int width, size_t* bytes);
 int vmv_gs_ssim_loss(const VmvGsSsimLossParams* p, void* stream);
+
+/* TSDF fusion of depth maps into a voxel volume (csrc/gs_tsdf.hip; videomv_amd/gs_mesh.py extracts the mesh from it).  Additive: the
+ * ABI version does not change, callers detect the entry by its symbol.  The volume is res^3 voxel CENTRES, centre (x, y, z) at
+ * origin + (x, y, z) * voxel, in seven fp32 planes [z][y][x] that the call reads, updates and writes back.
+ * One thread owns one voxel and walks the views in index order: no atomics, a deterministic function of the inputs; two calls give the
+ * same bits, and a volume integrated in two calls over views [0, k) and [k, V) equals one call over all V, bit for bit.
+ * For the voxel centre x and view v, in this order:
+ *   1. (xv, yv, z, _) = [x, 1] @ views[v]; z <= z_min: the view is skipped
+ *   2. px = ((xv / (z tan_half_fov) + 1) size - 1) / 2, likewise py (the rasteriser's pixel convention: a pixel centre is an INTEGER
+ *      px); ix = floor(px + 0.5), iy = floor(py + 0.5); outside [0, size)^2: skipped (tested on the float: near the camera plane px
+ *      is enormous)
+ *   3. d = depth[v][iy][ix];
+ *      d > 0:  sdf = d - z;  sdf < -trunc: n_behind += 1 (the voxel is hidden behind the surface), next view;
+ *              else sum_tsdf += min(1, sdf / trunc), W += 1, and if sdf <= trunc and colour is given:
+ *              sum_RGB += colour[v][:, iy, ix], Wc += 1
+ *      d == 0: carve: sum_tsdf += 1, W += 1 (the ray reached no surface: free space); else nothing
+ * Argument checks run before any launch and need no device: VMV_ENULL (p, depth, views or acc null), VMV_EINVAL (n_views < 1,
+ * size < 1, res outside [2, 1024], tan_half_fov / voxel / trunc / z_min not positive, plane_stride < res^3), VMV_ERANGE (size > 32768),
+ * VMV_EALIGN (a pointer not 4-byte aligned).  No allocation, no synchronisation. */
+typedef struct {
+    const float* depth;        /* [n_views][size][size] view depth z per pixel (render_depth's median_depth), 0 = no surface */
+    const float* colour;       /* [n_views][3][size][size] in [0,1], or NULL: colour planes untouched                        */
+    const float* views;        /* [n_views][16] cam_view, row-vector convention (as VmvGsBatchParams.views)                  */
+    int   n_views, size;
+    float tan_half_fov;
+    int   res;                 /* R: the volume is R x R x R voxel CENTRES                                                   */
+    float origin[3];           /* world position of voxel (x=0,y=0,z=0)'s centre; centre i is origin + i * voxel             */
+    float voxel, trunc, z_min; /* all > 0                                                                                    */
+    int   carve;               /* 1: a pixel without a surface observes free space                                           */
+    float* acc;                /* 7 planes [z][y][x] (x fastest), plane p at acc + p * plane_stride; read-modify-write:      */
+    long  plane_stride;        /*   0 sum tsdf, 1 W, 2 n_behind, 3..5 sum R G B, 6 Wc;   plane_stride >= R^3 (floats)       */
+} VmvGsTsdfParams;
+int vmv_gs_tsdf_integrate(const VmvGsTsdfParams* p, void* stream);   /* vmv_sizeof(109) */
 
 /* ------------------------------------------------------------------------------------------------------
  * Block permute-copy (frame-sharded sampling, DESIGN.md §8: packs / unpacks the all-to-all buffers that switch an

@@ -1,0 +1,104 @@
+"""ms per call of the TSDF fusion kernel (csrc/gs_tsdf.hip through gs_mesh.TsdfVolume.integrate) and of the mesh extraction
+(TsdfVolume.extract: the field + surface nets in torch on the device), on median-depth maps rendered from a seeded scene of 65 536
+Gaussians seen from V orbit views: (R, V, S) = (128, 24, 256) and (256, 48, 512) by default.  Next to the kernel's time, what it
+replaces: a torch-eager formulation of the same definition on the same GPU in the same process, one view at a time over the whole
+volume (it states the alternative; it is not a target).  Medians over --iters calls after --warmup.  Rates: the depth gathers the
+kernel issues (R^3 V, one per voxel and view) per second, and the plane bytes it moves (7 planes x R^3 x 4 B, read and written) per
+second.  Prints one JSON line per shape; --log FILE appends them to FILE.
+    python tools/gs_mesh_bench.py [--shapes 128:24:256,256:48:512] [--iters 30] [--warmup 5] [--gaussians 65536]"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools.gs_fit_bench import median_ms, orbit, scene  # noqa: E402
+
+
+def eager_integrate(acc, depth, colour, views, tan, origin, voxel, trunc, z_min, carve):
+    """the definition of include/vmv.h ("TSDF fusion") in torch eager, fp32 on the device, a view at a time; acc [7, R, R, R] in place"""
+    R, S = acc.shape[-1], depth.shape[-1]
+    i = torch.arange(R, dtype=torch.float32, device=acc.device)
+    wz, wy, wx = torch.meshgrid(origin[2] + i * voxel, origin[1] + i * voxel, origin[0] + i * voxel, indexing="ij")
+    for v, m in enumerate(views):                                       # m: 16 Python floats (no device read in the loop)
+        xv = wx * m[0] + wy * m[4] + wz * m[8] + m[12]
+        yv = wx * m[1] + wy * m[5] + wz * m[9] + m[13]
+        z = wx * m[2] + wy * m[6] + wz * m[10] + m[14]
+        zt = z * tan
+        fx, fy = torch.floor(((xv / zt + 1) * S - 1) * 0.5 + 0.5), torch.floor(((yv / zt + 1) * S - 1) * 0.5 + 0.5)
+        seen = (z > z_min) & (fx >= 0) & (fx < S) & (fy >= 0) & (fy < S)
+        pix = torch.nan_to_num(fy, nan=0.0).clamp(0, S - 1).long() * S + torch.nan_to_num(fx, nan=0.0).clamp(0, S - 1).long()
+        d = depth[v].reshape(-1)[pix]
+        sdf = d - z
+        surf = seen & (d > 0)
+        behind = surf & (sdf < -trunc)
+        fused = surf & ~behind
+        free = seen & (d == 0) if carve else torch.zeros_like(seen)
+        acc[2] += behind
+        acc[0] += torch.where(fused, (sdf / trunc).clamp(max=1.0), free.to(torch.float32))
+        acc[1] += fused | free
+        if colour is not None:
+            near = fused & (sdf <= trunc)
+            acc[3:6] += colour[v].reshape(3, -1)[:, pix] * near
+            acc[6] += near
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="128:24:256,256:48:512", help="R:V:S, comma-separated")
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--gaussians", type=int, default=65536)
+    ap.add_argument("--log", default=None)
+    args = ap.parse_args(argv)
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.log:
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            with open(args.log, "a") as fh:
+                fh.write(line + "\n")
+    from videomv_amd.entrance import _unpremultiplied
+    from videomv_amd.gs import GaussianRenderer
+    from videomv_amd.gs_mesh import TsdfVolume, mesh_stats
+    g = scene(args.gaussians, 1).cuda()
+    for R, V, S in (tuple(int(x) for x in s.split(":")) for s in args.shapes.split(",")):
+        cv, cvp = orbit(V)
+        r = GaussianRenderer(S)
+        out = r.render_depth(g.unsqueeze(0), cv.unsqueeze(0).cuda(), cvp.unsqueeze(0).cuda(), None, bg_color=torch.full((3,), 0.5).cuda())
+        depth, colour = out["median_depth"][0, :, 0].contiguous(), _unpremultiplied(out, 0.5).contiguous()
+        views = cv.cuda()
+        half = 2.0 * math.sin(0.5 * math.radians(r.fovy))
+        vol = TsdfVolume(R, half)
+        hip = median_ms(lambda: vol.integrate(depth, views, r.tan_half_fov, colour=colour), args.iters, args.warmup)
+        # one call each from zero: the mesh, and the eager formulation's planes against the kernel's
+        vol = TsdfVolume(R, half)
+        vol.integrate(depth, views, r.tan_half_fov, colour=colour)
+        res = {}
+        ext = median_ms(lambda: res.update(m=vol.extract()), 5, 1)
+        verts, _, faces = res["m"]
+        st = mesh_stats(verts, faces)
+        geo = ([float(torch.tensor(o, dtype=torch.float32)) for o in vol.origin], vol.voxel, vol.trunc)
+        vlist = [[float(x) for x in m.reshape(-1)] for m in cv]
+        acc = torch.zeros_like(vol.acc)
+        eager = median_ms(lambda: eager_integrate(acc, depth, colour, vlist, r.tan_half_fov, *geo, 0.05, True), max(3, args.iters // 3), 1)
+        acc.zero_()
+        eager_integrate(acc, depth, colour, vlist, r.tan_half_fov, *geo, 0.05, True)
+        torch.cuda.synchronize()
+        differ = float((acc[[1, 2, 6]] != vol.acc[[1, 2, 6]]).float().mean())
+        n, r3 = R ** 3, lambda t: [round(x, 4) for x in t]
+        emit(dict(res=R, views=V, size=S, gaussians=args.gaussians, pixels_with_depth=round(float((depth > 0).float().mean()), 4),
+                  integrate_ms=r3(hip), eager_ms=r3(eager), ms_are="median, min, max", eager_over_hip=round(eager[0] / hip[0], 2),
+                  depth_gathers_per_s=round(n * V / (hip[0] * 1e-3), 0), plane_bytes_per_s=round(7 * n * 4 * 2 / (hip[0] * 1e-3), 0),
+                  map_bytes=int(depth.numel() * 4 + colour.numel() * 4), plane_bytes=7 * n * 4 * 2,
+                  extract_ms=r3(ext), mesh=dict(vertices=st["vertices"], faces=st["faces"], open_edges=st["open_edges"], euler=st["euler"]),
+                  counts_that_differ_from_eager=differ, tsdf_max_diff_vs_eager=float((acc[0] - vol.acc[0]).abs().max())))
+
+
+if __name__ == "__main__":
+    main()

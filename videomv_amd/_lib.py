@@ -140,6 +140,12 @@ class GsSsimLossParams(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class GsTsdfParams(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("colour", C.c_void_p), ("views", C.c_void_p), ("n_views", C.c_int), ("size", C.c_int),
+                ("tan_half_fov", C.c_float), ("res", C.c_int), ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float),
+                ("z_min", C.c_float), ("carve", C.c_int), ("acc", C.c_void_p), ("plane_stride", C.c_long)]
+
+
 class CopyParams(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("inner16", C.c_int32), ("ss0", C.c_int64), ("ss1", C.c_int64), ("ss2", C.c_int64)]
@@ -232,6 +238,7 @@ SYMBOLS = {
     "vmv_gs_adam_step": (C.c_int, [C.POINTER(GsAdamParams), _P]),
     "vmv_gs_ssim_loss_workspace_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "vmv_gs_ssim_loss": (C.c_int, [C.POINTER(GsSsimLossParams), _P]),
+    "vmv_gs_tsdf_integrate": (C.c_int, [C.POINTER(GsTsdfParams), _P]),
     "vmv_latent_to_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_latent_to_rows_keep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_i2v_temporal_adapter": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
@@ -286,7 +293,7 @@ def load():
     if lib.vmv_elem_type() != (ELEM_F16 if _elem == "f16" else ELEM_BF16):
         raise RuntimeError(f"{LIB_PATH} was built for another element type")
     for which, st in ((OP_GEMM, GemmParams), (OP_GN_STATS, GroupNormParams), (OP_LAYERNORM, LayerNormParams),
-                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (108, GsDepthParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
+                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (108, GsDepthParams), (109, GsTsdfParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
         if lib.vmv_sizeof(which) != C.sizeof(st):
             raise RuntimeError(f"struct layout drift for {st.__name__}: C {lib.vmv_sizeof(which)} vs ctypes "
                                f"{C.sizeof(st)}")

@@ -76,6 +76,10 @@ def default_cfg() -> AttrDict:
     c.gs_orbit_depth = False          # also write the orbit's median-depth maps: <stem>_gs_orbit_depth.npy / .png (GaussianRenderer.render_depth)
     c.gs_points = False               # also write the point cloud those depth maps unproject to: <stem>_gs_points.ply
     c.gs_points_voxel = None          # its merge voxel (None: 1/256 of the width the orbit camera sees at the origin's distance)
+    c.gs_mesh = False                 # also write the coloured triangle mesh those depth maps fuse to: <stem>_gs_mesh.ply (gs_mesh.py)
+    c.gs_mesh_res = 128               # voxels per side of the fusion volume, 16 .. 512
+    c.gs_mesh_extent = None           # half-width of its cube (None: d sin(fovy / 2), the ball every orbit view sees whole)
+    c.gs_mesh_trunc = None            # truncation distance of the TSDF (None: 3 voxels)
     return c
 
 

@@ -60,6 +60,7 @@ extern "C" int vmv_sizeof(int which) {
         case 106: return (int)sizeof(VmvGsAdamParams);
         case 107: return (int)sizeof(VmvGsSsimLossParams);
         case 108: return (int)sizeof(VmvGsDepthParams);
+        case 109: return (int)sizeof(VmvGsTsdfParams);
         default: return (int)op_size(which);
     }
 }

@@ -12,6 +12,7 @@ plus a ``.pt`` tensor and a PNG contact sheet; the second, LGM-refined loop (:27
 runs when ``UNet.use_lgm_refine`` is set (also under ``frame_parallel``; not under ``cfg_parallel``).
 """
 import logging
+import math
 import os
 import os.path as osp
 import re
@@ -393,14 +394,25 @@ def worker_i2v(gpu, cfg, cfg_update):
 def _check_export_cfg(cfg, use_lgm):
     """`save_gaussians` (not a reference key) exports the LGM-refined loop's Gaussians: refuse it, before any sampling, where that loop
     does not run or cannot run (the LGM renders square views only), or where the fit's objective is not one the fitter knows."""
-    geometry = [k for k in ('gs_orbit_depth', 'gs_points', 'gs_points_voxel') if cfg.get(k)]
+    geometry = [k for k in ('gs_orbit_depth', 'gs_points', 'gs_points_voxel', 'gs_mesh') if cfg.get(k)]
     if geometry and not (cfg.get('save_gaussians') and int(cfg.get('gs_orbit_views') or 0) > 0):
-        raise ValueError(f"{' / '.join(geometry)}: depth maps and the point cloud come from the orbit render of the exported Gaussians: "
-                         "set save_gaussians True and gs_orbit_views > 0")
+        raise ValueError(f"{' / '.join(geometry)}: depth maps, the point cloud and the mesh come from the orbit render of the exported "
+                         "Gaussians: set save_gaussians True and gs_orbit_views > 0")
     if cfg.get('gs_points_voxel') and not cfg.get('gs_points'):
         raise ValueError("gs_points_voxel is the voxel size of the gs_points export: set gs_points True")
     if cfg.get('gs_points_voxel') is not None and cfg.get('gs_points') and not float(cfg.get('gs_points_voxel')) > 0:
         raise ValueError(f"gs_points_voxel must be positive, got {cfg.get('gs_points_voxel')}")
+    if not cfg.get('gs_mesh'):
+        sub = [k for k in ('gs_mesh_extent', 'gs_mesh_trunc') if cfg.get(k) is not None]
+        sub += ['gs_mesh_res'] if int(cfg.get('gs_mesh_res') or 128) != 128 else []
+        if sub:
+            raise ValueError(f"{' / '.join(sub)}: a setting of the gs_mesh export: set gs_mesh True")
+    else:
+        if not 16 <= int(cfg.get('gs_mesh_res') or 128) <= 512:
+            raise ValueError(f"gs_mesh_res must be in [16, 512], got {cfg.get('gs_mesh_res')}")
+        for k in ('gs_mesh_extent', 'gs_mesh_trunc'):
+            if cfg.get(k) is not None and not float(cfg.get(k)) > 0:
+                raise ValueError(f"{k} must be positive, got {cfg.get(k)}")
     if not cfg.get('save_gaussians'):
         return
     if not use_lgm:
@@ -425,8 +437,9 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
     """The 3-D asset of one LGM-refined sample: the LGM on its final key views (LgmRefiner.gaussians_from_views), optionally fitted to
     all its decoded views (gs_fit.GaussianFitter: targets video * 0.5 + 0.5 against the refiner's background), written as
     ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit; with ``gs_orbit_depth``
-    / ``gs_points`` that orbit is rendered ONCE in the rasteriser's depth mode and its median-depth maps (``_gs_orbit_depth.npy`` /
-    ``.png``) and the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) are written too.  Draws nothing from
+    / ``gs_points`` / ``gs_mesh`` that orbit is rendered ONCE in the rasteriser's depth mode and its median-depth maps
+    (``_gs_orbit_depth.npy`` / ``.png``), the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) and the coloured
+    triangle mesh they fuse to (``_gs_mesh.ply``: TSDF fusion + surface nets on the device, gs_mesh.py) are written too.  Draws nothing from
     the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
     from .gs import GaussianRenderer
     from .lgm import orbit_cameras
@@ -462,7 +475,7 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
         cv, cvp = orbit_cameras(camera_data, n_orbit, elev, camera_dist, opt)
         bgc = torch.full((3,), refiner.bg_color, dtype=torch.float32, device=device)
         renderer = GaussianRenderer(size, opt.fovy, opt.znear, opt.zfar)
-        geometry = bool(cfg.get('gs_orbit_depth') or cfg.get('gs_points'))
+        geometry = bool(cfg.get('gs_orbit_depth') or cfg.get('gs_points') or cfg.get('gs_mesh'))
         out = (renderer.render_depth if geometry else renderer.render)(g.to(device), cv.to(device), cvp.to(device), None, bg_color=bgc)
         img = out["image"]
         mean, std = torch.tensor(cfg.mean).view(1, 3, 1, 1, 1), torch.tensor(cfg.std).view(1, 3, 1, 1, 1)
@@ -482,6 +495,20 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
             rec['points_ply'] = stem + '_gs_points.ply'
             rec['points'] = _export_points(out, cv[0], renderer.tan_half_fov, refiner.bg_color, voxel, rec['points_ply'])
             logging.info(f"Save point cloud ({rec['points']} points, voxel {voxel:.5f}) to {rec['points_ply']}")
+        if cfg.get('gs_mesh'):
+            from .gs_mesh import TsdfVolume, mesh_stats, save_mesh_ply
+            res, half, trunc = int(cfg.get('gs_mesh_res') or 128), cfg.get('gs_mesh_extent'), cfg.get('gs_mesh_trunc')
+            # default cube: the ball every orbit view sees whole, d sin(fovy / 2) around the origin of the Gaussians' frame
+            cam_dist = float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
+            half = cam_dist * math.sin(0.5 * math.radians(opt.fovy)) if half is None else float(half)
+            vol = TsdfVolume(res, half, trunc=None if trunc is None else float(trunc), device=device)
+            vol.integrate(out["median_depth"][0, :, 0], cv[0], renderer.tan_half_fov, colour=_unpremultiplied(out, refiner.bg_color))
+            verts, cols, faces = vol.extract()
+            rec['mesh_ply'] = stem + '_gs_mesh.ply'
+            rec['mesh_vertices'], rec['mesh_faces'] = save_mesh_ply(verts, cols, faces, rec['mesh_ply'])
+            rec['mesh_open_edges'] = mesh_stats(verts, faces)['open_edges']
+            logging.info(f"Save mesh ({rec['mesh_vertices']} vertices, {rec['mesh_faces']} faces, {rec['mesh_open_edges']} open edges; "
+                         f"{res}^3 voxels of {vol.voxel:.5f}, {n_orbit} views fused) to {rec['mesh_ply']}")
     return rec
 
 
@@ -500,18 +527,24 @@ def _save_depth_maps(depth, npy_path, png_path, znear, zfar):
         logging.info(f'Step: save png error with {e}')
 
 
+def _unpremultiplied(out, bg):
+    """The colour of the surface in every view of ``out`` (GaussianRenderer.render_depth, sample 0), the background taken out:
+    clamp((image - (1 - alpha) bg) / alpha, 0, 1) -> [V, 3, S, S]"""
+    a = out["alpha"][0]
+    return ((out["image"][0] - (1.0 - a) * bg) / a.clamp_min(1e-6)).clamp(0, 1)
+
+
 def _export_points(out, cam_view, tan_half_fov, bg, voxel, path):
     """The pixels of every view of ``out`` (GaussianRenderer.render_depth, sample 0) that have a median depth, unprojected to world
-    points and coloured with the un-premultiplied render clamp((image - (1 - alpha) bg) / alpha, 0, 1), merged per voxel, written as a
-    .ply.  Deterministic, no RNG.  -> the number of points."""
+    points and coloured with the un-premultiplied render (``_unpremultiplied``), merged per voxel, written as a .ply.  Deterministic,
+    no RNG.  -> the number of points."""
     from .gs import depth_to_points, merge_points_voxel, save_points_ply
+    colour = _unpremultiplied(out, bg)
     pts, cols = [], []
     for v in range(cam_view.shape[0]):
         p, idx = depth_to_points(out["median_depth"][0, v, 0], cam_view[v], tan_half_fov)
-        a = out["alpha"][0, v, 0].reshape(-1)[idx]
-        c = out["image"][0, v].reshape(3, -1)[:, idx]
         pts.append(p)
-        cols.append(((c - (1.0 - a) * bg) / a.clamp_min(1e-6)).clamp(0, 1).t())
+        cols.append(colour[v].reshape(3, -1)[:, idx].t())
     pts, cols = torch.cat(pts).float().cpu(), torch.cat(cols).float().cpu()
     if pts.shape[0] > 0:
         pts, cols = merge_points_voxel(pts, cols, voxel)

@@ -1,0 +1,200 @@
+"""A coloured triangle mesh from depth maps: TSDF fusion on the gfx950 kernel (``csrc/gs_tsdf.hip``, contract in ``include/vmv.h``)
+and naive surface nets over the fused field, in vectorised torch on the device the accumulators live on.
+
+``TsdfVolume`` owns the seven accumulator planes of ``VmvGsTsdfParams`` and turns them into a signed field; ``surface_nets`` places one
+vertex per sign-changing cell and one quad per sign-changing grid edge; ``mesh_stats`` counts what a consumer would trip over (open and
+misoriented edges, the Euler characteristic, the signed volume); ``save_mesh_ply`` / ``load_mesh_ply`` are the binary little-endian
+writer and its inverse.  No RNG anywhere: the same inputs give the same file.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+PLANES = ("tsdf", "weight", "behind", "red", "green", "blue", "colour_weight")
+
+
+class TsdfVolume:
+    """res^3 voxel CENTRES over the cube centre +- half_extent: voxel = 2 half_extent / res, centre i at origin + i * voxel with
+    origin = centre - half_extent + voxel / 2.  ``acc`` [7, res, res, res] (planes of VmvGsTsdfParams, [z][y][x]) starts at zero."""
+
+    def __init__(self, res, half_extent, centre=(0.0, 0.0, 0.0), trunc=None, device="cuda"):
+        self.res = int(res)
+        self.voxel = 2.0 * float(half_extent) / self.res
+        self.origin = tuple(float(c) - float(half_extent) + 0.5 * self.voxel for c in centre)
+        self.trunc = 3.0 * self.voxel if trunc is None else float(trunc)
+        self.acc = torch.zeros(7, self.res, self.res, self.res, dtype=torch.float32, device=device)
+        self.n_views = 0
+
+    @torch.no_grad()
+    def integrate(self, depth, cam_view, tan_half_fov, colour=None, carve=True, z_min=0.05):
+        """Fuse ``depth`` [V, S, S] (view depth per pixel, 0 = no surface) seen through ``cam_view`` [V, 4, 4] (row-vector convention),
+        with ``colour`` [V, 3, S, S] if given, into the volume: one launch of vmv_gs_tsdf_integrate on the current stream."""
+        from .ops import _stream_ptr
+        dev = self.acc.device
+        if dev.type != "cuda":
+            raise RuntimeError("TsdfVolume.integrate runs the HIP kernel: the volume must live on a GPU (there is no CPU fallback)")
+        V, S = int(depth.shape[0]), int(depth.shape[-1])
+        d = depth.to(dev, torch.float32).reshape(V, S, S).contiguous()
+        views = cam_view.to(dev, torch.float32).reshape(V, 16).contiguous()
+        col = None if colour is None else colour.to(dev, torch.float32).reshape(V, 3, S, S).contiguous()
+        p = L.GsTsdfParams()
+        p.depth, p.colour, p.views = d.data_ptr(), None if col is None else col.data_ptr(), views.data_ptr()
+        p.n_views, p.size, p.tan_half_fov, p.res = V, S, float(tan_half_fov), self.res
+        p.origin[0], p.origin[1], p.origin[2] = self.origin
+        p.voxel, p.trunc, p.z_min, p.carve = self.voxel, self.trunc, float(z_min), 1 if carve else 0
+        p.acc, p.plane_stride = self.acc.data_ptr(), self.res ** 3
+        L.check(L.load().vmv_gs_tsdf_integrate(C.byref(p), _stream_ptr()), "gs_tsdf_integrate")
+        self.n_views += V
+
+    def field(self, min_weight=1):
+        """-> (f, valid) [res, res, res]: f = sum tsdf / W where W >= min_weight; f = -1 where the voxel was never in front of or near a
+        surface (W == 0) and hidden behind one in EVERY view integrated (n_behind == n_views): solid; every other voxel is invalid
+        (f = 0 there).  "Every", not "any": a voxel that leaves some view's frustum is not known to be solid."""
+        tsdf, w, behind = self.acc[0], self.acc[1], self.acc[2]
+        seen = w >= float(min_weight)
+        solid = (w == 0) & (behind == float(self.n_views)) & (self.n_views > 0)
+        f = torch.where(seen, tsdf / w.clamp_min(1.0), torch.where(solid, -torch.ones_like(w), torch.zeros_like(w)))
+        return f, seen | solid
+
+    def colours(self):
+        """-> [3, res, res, res]: sum RGB / Wc, 0.5 where Wc == 0"""
+        wc = self.acc[6]
+        return torch.where(wc > 0, self.acc[3:6] / wc.clamp_min(1.0), torch.full_like(self.acc[3:6], 0.5))
+
+    def extract(self, min_weight=1):
+        """-> (verts [n, 3] fp32, colours [n, 3], faces [m, 3] int64) on the volume's device"""
+        f, valid = self.field(min_weight)
+        return surface_nets(f, valid, self.origin, self.voxel, colour=self.colours(), colour_weight=self.acc[6])
+
+
+# the 8 corners of a cell as (dz, dy, dx), corner c = 4 dz + 2 dy + dx, and its 12 edges (corner pairs that differ in one bit)
+_CORNERS = [(c >> 2 & 1, c >> 1 & 1, c & 1) for c in range(8)]
+_EDGES = [(a, a | b) for a in range(8) for b in (1, 2, 4) if not a & b]
+# grid edges along tensor dim a; (u, v) are the two other dims with e_a = e_u x e_v in the right-handed (x, y, z) = dims (2, 1, 0)
+_AXES = ((2, 1, 0), (1, 0, 2), (0, 2, 1))
+
+
+@torch.no_grad()
+def surface_nets(f, valid, origin, voxel, colour=None, colour_weight=None):
+    """Naive surface nets over the field ``f`` [R, R, R] ([z][y][x]; negative inside) at voxel centres origin + i * voxel.
+    A cell (the cube between 8 neighbouring centres) is active if all 8 corners are ``valid`` and the signs of f < 0 are mixed; its
+    vertex is the mean of the linear zero crossings t = f0 / (f0 - f1) on its sign-changing edges, its colour the ``colour_weight``-
+    weighted mean of the 8 corner colours (``colour`` [3, R, R, R]; the plain mean where the weights sum to 0; 0.5 without ``colour``).
+    Every grid edge whose ends differ in sign and whose four surrounding cells are all active emits the quad of their vertices as two
+    triangles, wound so that the normal points from f < 0 to f > 0.  Vertices that no triangle uses are dropped.  Order: cells and
+    edges row-major, x edges, then y, then z.  Runs on f's device.  -> (verts [n, 3] fp32 (x, y, z), colours [n, 3], faces [m, 3] int64)."""
+    R, dev = int(f.shape[0]), f.device
+    assert tuple(f.shape) == (R, R, R) and tuple(valid.shape) == (R, R, R) and R >= 2
+    f = f.to(torch.float32)
+    inside = f < 0
+    n = R - 1
+    cell = lambda t, c: t[c[0]:c[0] + n, c[1]:c[1] + n, c[2]:c[2] + n]
+    n_in = torch.zeros(n, n, n, dtype=torch.int8, device=dev)
+    ok = torch.ones(n, n, n, dtype=torch.bool, device=dev)
+    for c in _CORNERS:
+        n_in += cell(inside, c).to(torch.int8)
+        ok &= cell(valid, c)
+    active = ok & (n_in > 0) & (n_in < 8)
+    zyx = active.nonzero()                                              # [k, 3] row-major
+    k = int(zyx.shape[0])
+    cid = torch.full((n, n, n), -1, dtype=torch.int64, device=dev)
+    cid[active] = torch.arange(k, device=dev)
+    # corner values of the active cells, by flat index into [R, R, R]
+    offs = torch.tensor([(dz * R + dy) * R + dx for dz, dy, dx in _CORNERS], device=dev)
+    idx8 = ((zyx[:, 0] * R + zyx[:, 1]) * R + zyx[:, 2])[:, None] + offs[None, :]          # [k, 8]
+    fc = f.reshape(-1)[idx8]
+    ea, eb = (torch.tensor([e[i] for e in _EDGES], device=dev) for i in (0, 1))
+    fa, fb = fc[:, ea], fc[:, eb]
+    cross = (fa < 0) != (fb < 0)
+    t = torch.where(cross, fa / torch.where(cross, fa - fb, torch.ones_like(fa)), torch.zeros_like(fa))
+    cp = torch.tensor([[dx, dy, dz] for dz, dy, dx in _CORNERS], dtype=torch.float32, device=dev)     # (x, y, z)
+    pts = cp[ea][None] + t[..., None] * (cp[eb] - cp[ea])[None]                                        # [k, 12, 3]
+    w = cross.to(torch.float32)
+    local = (pts * w[..., None]).sum(1) / w.sum(1, keepdim=True).clamp_min(1.0)
+    verts = torch.tensor(list(origin), dtype=torch.float32, device=dev) + (zyx.flip(1).to(torch.float32) + local) * float(voxel)
+    if colour is None:
+        cols = torch.full((k, 3), 0.5, dtype=torch.float32, device=dev)
+    else:
+        cc = colour.to(torch.float32).reshape(3, -1)[:, idx8]                                          # [3, k, 8]
+        cw = torch.ones_like(fc) if colour_weight is None else colour_weight.to(torch.float32).reshape(-1)[idx8]
+        ws = cw.sum(1)
+        cols = torch.where(ws > 0, (cc * cw).sum(2) / ws.clamp_min(1e-20), cc.mean(2)).t().contiguous()
+    faces = []
+    m = R - 2
+    for a, u, v in _AXES:
+        inner = lambda x: x.narrow(u, 1, m).narrow(v, 1, m)
+        lo, hi = inner(inside.narrow(a, 0, n)), inner(inside.narrow(a, 1, n))
+        quad = [cid.narrow(u, du, m).narrow(v, dv, m) for du, dv in ((0, 0), (1, 0), (1, 1), (0, 1))]   # counter-clockwise seen from +a
+        emit = lo != hi
+        for q in quad:
+            emit = emit & (q >= 0)
+        q = torch.stack([c[emit] for c in quad], dim=1)                                                # [e, 4]
+        q = torch.where(lo[emit][:, None], q, q[:, [0, 3, 2, 1]])                                      # inside at the low end: normal along +a
+        faces.append(torch.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], dim=1).reshape(-1, 3))
+    faces = torch.cat(faces)
+    used = torch.unique(faces)                                          # sorted: the vertex order is kept
+    remap = torch.full((k,), -1, dtype=torch.int64, device=dev)
+    remap[used] = torch.arange(int(used.shape[0]), device=dev)
+    return verts[used], cols[used], remap[faces]
+
+
+def mesh_stats(verts, faces):
+    """-> dict: vertices, edges (undirected), faces, euler = V - E + F, open_edges (undirected edges not in exactly two triangles),
+    misoriented (directed edges that occur more than once: two neighbours wound against each other), volume (signed: positive for
+    outward normals)."""
+    v, f = verts.detach().cpu().double(), faces.detach().cpu().long()
+    nv = max(int(v.shape[0]), 1)
+    d = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    _, dc = torch.unique(d[:, 0] * nv + d[:, 1], return_counts=True)
+    _, uc = torch.unique(d.min(1).values * nv + d.max(1).values, return_counts=True)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    E = int(uc.shape[0])
+    return dict(vertices=int(v.shape[0]), edges=E, faces=int(f.shape[0]), euler=int(v.shape[0]) - E + int(f.shape[0]),
+                open_edges=int((uc != 2).sum()), misoriented=int((dc > 1).sum()),
+                volume=float((a * torch.linalg.cross(b, c)).sum() / 6.0))
+
+
+_VERTEX = [("xyz", "<f4", 3), ("rgb", "u1", 3)]                         # 15 bytes
+_FACE = [("n", "u1"), ("idx", "<i4", 3)]                                # 13 bytes
+_HEADER = (["property float %s" % a for a in "xyz"] + ["property uchar %s" % a for a in ("red", "green", "blue")],
+           ["property list uchar int vertex_indices"])
+
+
+def save_mesh_ply(verts, colours, faces, path):
+    """verts [n, 3] fp32, colours [n, 3] in [0, 1], faces [m, 3] -> binary little-endian .ply: x y z float32 and red green blue uchar
+    (rounded as save_points_ply rounds) per vertex, a uchar count of 3 and three int32 indices per face.  -> (n, m)."""
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    vr = np.empty(n, dtype=_VERTEX)
+    vr["xyz"] = verts.detach().float().cpu().numpy()
+    vr["rgb"] = (colours.detach().float().cpu().clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).numpy()
+    fr = np.empty(m, dtype=_FACE)
+    fr["n"] = 3
+    fr["idx"] = faces.detach().cpu().numpy().astype("<i4")
+    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + _HEADER[0] + ["element face %d" % m] + _HEADER[1]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(lines) + "\nend_header\n").encode("ascii"))
+        fh.write(vr.tobytes())
+        fh.write(fr.tobytes())
+    return n, m
+
+
+def load_mesh_ply(path):
+    """The inverse of ``save_mesh_ply`` -> (verts [n, 3] fp32, colours [n, 3] uint8, faces [m, 3] int64)."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    elems = [i for i, ln in enumerate(lines) if ln.startswith("element")]
+    if (lines[:2] != ["ply", "format binary_little_endian 1.0"] or len(elems) != 2 or not lines[elems[0]].startswith("element vertex ")
+            or not lines[elems[1]].startswith("element face ") or lines[elems[0] + 1:elems[1]] != _HEADER[0]
+            or lines[elems[1] + 1:-1] != _HEADER[1]):
+        raise ValueError(f"{path}: not a mesh written by save_mesh_ply")
+    n, m = int(lines[elems[0]].split()[2]), int(lines[elems[1]].split()[2])
+    vr = np.frombuffer(data, dtype=_VERTEX, count=n, offset=end)
+    fr = np.frombuffer(data, dtype=_FACE, count=m, offset=end + 15 * n)
+    if m and not (fr["n"] == 3).all():
+        raise ValueError(f"{path}: faces that are not triangles")
+    return torch.from_numpy(vr["xyz"].copy()), torch.from_numpy(vr["rgb"].copy()), torch.from_numpy(fr["idx"].astype(np.int64))
