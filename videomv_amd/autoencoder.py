@@ -24,7 +24,7 @@ from .registry import AUTO_ENCODER
 from . import _lib as L
 from . import ops
 from . import packing as P
-from .unet_engine import Pool, Act
+from .plan_builder import Act, PlanBuilder
 from .unet_t2v import _Holder
 
 
@@ -85,23 +85,18 @@ def vae_param_shapes(dd: dict, embed_dim: int) -> Dict[str, tuple]:
     return dict(s)
 
 
-class _VaeEngine:
+class _VaeEngine(PlanBuilder):
     """Shared pieces of the decoder / encoder plans: packing, GroupNorm(1e-6)+swish, ResnetBlock, 1-head AttnBlock."""
+
+    SPLITK_CAP = 32
 
     def __init__(self, dd: dict, sd: Dict[str, torch.Tensor], n: int, h: int, w: int, device, packed=None):
         """packed: the .wt of another engine of the same kind, model and device — packed weights are immutable and
         shape-independent, so the engines of one model (other frame counts / resolutions) share ONE copy."""
-        self.dd, self.n, self.h, self.w, self.device = dd, n, h, w, device
-        self.pool = Pool(device)
-        self.S = ops.Stream(record=True)
-        self.S.tuner = ops.make_tuner(self)      # measured per-shape (tile, split-K) choices: videomv_amd/tuned_gemm.json
-        self._keep = []
-        self._gnws = torch.empty(4 << 20, dtype=torch.float32, device=device)
-        if packed is not None:
-            self.wt = packed
-        else:
-            self.wt = {}
-            self._pack(sd)
+        self.dd, self.n, self.h, self.w = dd, n, h, w      # (w: the width — the packed weights are .wt)
+        self._init_plan(device)
+        self._take_weights(sd, packed)
+        if packed is None:
             P.check_finite_weights(self.wt, type(self).__name__)
         self._build()
 
@@ -137,58 +132,13 @@ class _VaeEngine:
 
         return conv, norm, lin, res, attn
 
-
-    # ---- helpers
-    def act(self, rows, C, dtype=None):
-        return Act(self.pool.get(rows * C * (4 if dtype == torch.float32 else 2)), rows, C, dtype)
-
-    def rel(self, a):
-        self.pool.put(a.buf)
-
-    def _gemm(self, label, M, segs, wkey, out, ldo=None, bias=None, N=None, **kw):
-        """wkey: name of a packed weight, or a raw device pointer to 16-bit [N][K] rows (then N must be given)."""
-        W = self.wt[wkey] if isinstance(wkey, str) else wkey
-        if N is None:
-            N = W.shape[0]
-        if "ksplit" not in kw and not kw.get("rowstat"):
-            if getattr(self, "_splitk", None) is None:
-                self._splitk = ops.SplitK(self.device if hasattr(self, "device") else self.dev, cap=32)
-            kw["ksplit"], kw["workspace"] = self._splitk.pick(M, N, segs)
-        self.S.gemm(ops.gemm_params(M, N, segs, W, out.ptr if isinstance(out, Act) else out,
-                                    ldo if ldo is not None else out.C, bias=bias, **kw), label)
-
-    def _gn(self, label, x: Act, rows_per_stat, key, silu):
-        y = self.act(x.rows, x.C)
-        assert ops.gn_partial_floats(x.rows, rows_per_stat, x.C) <= self._gnws.numel()
-        self.S.groupnorm(ops.gn_params(x.ptr, x.C, x.C, x.rows, rows_per_stat, self._gnws, self.wt[key + ".weight"],
-                                       self.wt[key + ".bias"], 1e-6, silu, y.ptr, y.C), label)
-        return y
-
+    # ---- blocks
     def _res(self, p, x: Act, h, w) -> Act:
-        T = x.rows
-        geom = ops.Geom(OH=h, OW=w, IH=h, IW=w)
-        cout = self.wt[p + ".conv1.weight"].shape[0]
-        h0 = self._gn(p + ".norm1", x, h * w, p + ".norm1", True)
-        h1 = self.act(T, cout)
-        self._gemm(p + ".conv1", T, ops.conv3x3_segs([(h0.ptr, h0.C, h0.C)]), p + ".conv1.weight", h1,
-                   bias=self.wt[p + ".conv1.bias"], geom=geom)
-        self.rel(h0)
-        h2 = self._gn(p + ".norm2", h1, h * w, p + ".norm2", True)
-        self.rel(h1)
-        y = self.act(T, cout)
-        segs = ops.conv3x3_segs([(h2.ptr, h2.C, h2.C)])
-        if x.C != cout:
-            segs += ops.linear_segs([(x.ptr, x.C, x.C)])
-            self._gemm(p + ".conv2+nin", T, segs, p + ".conv2.weight", y, bias=self.wt[p + ".conv2.bias"], geom=geom)
-        else:
-            self._gemm(p + ".conv2", T, segs, p + ".conv2.weight", y, bias=self.wt[p + ".conv2.bias"], geom=geom,
-                       residual=x.ptr, ldr=x.C)
-        self.rel(h2)
-        return y
+        return self._conv_res(p, [x], h, w, 1e-6, "nin")
 
     def _attn(self, p, x: Act, h, w) -> Act:
         n, hw, C, T = self.n, h * w, x.C, x.rows
-        hn = self._gn(p + ".norm", x, hw, p + ".norm", False)
+        hn = self._gn(p + ".norm", [x], hw, p + ".norm", 1e-6, False)
         q, k = self.act(T, C), self.act(T, C)
         lin = ops.linear_segs([(hn.ptr, C, C)])
         self._gemm(p + ".q", T, lin, p + ".q.weight", q, bias=self.wt[p + ".q.bias"])
@@ -292,14 +242,10 @@ class VaeDecoderEngine(_VaeEngine):
             for i in range(nrb + 1):
                 step(lambda: self._res(f"decoder.up.{lvl}.block.{i}", x, h, w))
             if lvl != 0:
-                p = f"decoder.up.{lvl}.upsample.conv"
-                y = self.act(n * 4 * h * w, x.C)
-                self._gemm(p, y.rows, ops.conv3x3_segs([(x.ptr, x.C, x.C)]), p + ".weight", y, bias=self.wt[p + ".bias"],
-                           geom=ops.Geom(OH=2 * h, OW=2 * w, IH=h, IW=w, ups=1))
+                y, oh, ow = self._conv_up(f"decoder.up.{lvl}.upsample.conv", x, h, w)
                 self.rel(x)
-                x = y
-                h, w = 2 * h, 2 * w
-        hn = self._gn("norm_out", x, h * w, "decoder.norm_out", True)
+                x, h, w = y, oh, ow
+        hn = self._gn("norm_out", [x], h * w, "decoder.norm_out", 1e-6, True)
         self.rel(x)
         self.OH, self.OW = h, w
         self.img_rows = torch.zeros(n * h * w, self.out_pad, dtype=torch.float32, device=dev)
@@ -353,18 +299,14 @@ class VaeEncoderEngine(_VaeEngine):
                 self.rel(x)
                 x = y
             if lvl != len(ch_mult) - 1:
-                p = f"encoder.down.{lvl}.downsample.conv"
-                oh, ow = h // 2, w // 2
-                y = self.act(n * oh * ow, x.C)
-                self._gemm(p, y.rows, ops.conv3x3_segs([(x.ptr, x.C, x.C)], shift=1), p + ".weight", y,
-                           bias=self.wt[p + ".bias"], geom=ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=2))
+                y, oh, ow = self._conv_down(f"encoder.down.{lvl}.downsample.conv", x, h, w, shift=1)
                 self.rel(x)
                 x, h, w = y, oh, ow
         for fn, p in ((self._res, "encoder.mid.block_1"), (self._attn, "encoder.mid.attn_1"), (self._res, "encoder.mid.block_2")):
             y = fn(p, x, h, w)
             self.rel(x)
             x = y
-        hn = self._gn("norm_out", x, h * w, "encoder.norm_out", True)
+        hn = self._gn("norm_out", [x], h * w, "encoder.norm_out", 1e-6, True)
         self.rel(x)
         T = n * h * w
         co = self.act(T, self.wt["encoder.conv_out.weight"].shape[0])

@@ -22,7 +22,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing as P
-from .unet_engine import Pool, Act
+from .plan_builder import Act, PlanBuilder
 
 
 @dataclasses.dataclass
@@ -50,16 +50,9 @@ def clip_text_shapes(o: ClipTextOptions) -> Dict[str, tuple]:
     return s
 
 
-class _ClipTower:
-    """Shared by the text and image towers: pooled activations, the recorded stream, and open_clip's ResidualAttentionBlock
-    (``x = x + attn(ln_1(x))``, ``x = x + c_proj(gelu(c_fc(ln_2(x))))``) as 7 launches."""
-
-    def _init_common(self, device, taps):
-        self.device, self.taps = device, taps
-        self.pool = Pool(device)
-        self.S = ops.Stream(record=True)
-        self._splitk = ops.SplitK(device, cap=8)
-        self.wt: Dict[str, torch.Tensor] = {}
+class _ClipTower(PlanBuilder):
+    """Shared by the text and image towers: open_clip's ResidualAttentionBlock (``x = x + attn(ln_1(x))``,
+    ``x = x + c_proj(gelu(c_fc(ln_2(x))))``) as 7 launches."""
 
     def _pack_or_share(self, sd, donor):
         """Packed weights are immutable and batch-size independent: an engine for another B of the same tower takes its donor's copy
@@ -70,21 +63,11 @@ class _ClipTower:
             for a in self._PACKED_ATTRS:
                 setattr(self, a, getattr(donor, a))
         else:
+            self.wt: Dict[str, torch.Tensor] = {}
             self._pack(sd)
 
-    def act(self, rows, C, dtype=None) -> Act:
-        return Act(self.pool.get(rows * C * (4 if dtype == torch.float32 else 2)), rows, C, dtype)
-
-    def rel(self, a: Act):
-        if self.taps is None and not getattr(a, "_pinned", False):
-            self.pool.put(a.buf)
-
-    def _gemm(self, label, x: Act, wkey, out: Act, **kw):
-        Wt = self.wt[wkey + ".weight"]
-        segs = ops.linear_segs([(x.ptr, x.C, x.C)])
-        ks, ws = self._splitk.pick(x.rows, Wt.shape[0], segs)
-        self.S.gemm(ops.gemm_params(x.rows, Wt.shape[0], segs, Wt, out.ptr, out.C, bias=self.wt.get(wkey + ".bias"),
-                                    ksplit=ks, workspace=ws, **kw), label)
+    def _linear(self, label, x: Act, wkey, out: Act, **kw):
+        self._gemm(label, x.rows, ops.linear_segs([(x.ptr, x.C, x.C)]), wkey + ".weight", out, bias=self.wt.get(wkey + ".bias"), **kw)
 
     def _ln(self, label, x: Act, key) -> Act:
         y = self.act(x.rows, x.C)
@@ -115,7 +98,7 @@ class _ClipTower:
         rows, W, A = x.rows, x.C, heads * hdp
         h = self._ln(p + "ln_1", x, p + "ln_1")
         qkv = self.act(rows, 3 * A)
-        self._gemm(p + "qkv", h, p + "qkv", qkv)
+        self._linear(p + "qkv", h, p + "qkv", qkv)
         self.rel(h)
         ao = self.act(rows, A)
         m = lambda: ops.seq_map(T * 3 * A, 0, 3 * A, inner=1)
@@ -123,17 +106,17 @@ class _ClipTower:
                                          B, heads, T, T, hd ** -0.5, head_dim=hdp, causal=causal), p + "attn")
         self.rel(qkv)
         y = self.act(rows, W)
-        self._gemm(p + "out", ao, p + "out", y, residual=x.ptr, ldr=W)
+        self._linear(p + "out", ao, p + "out", y, residual=x.ptr, ldr=W)
         self.rel(ao)
         if release_x:
             self.rel(x)
         x = y
         h = self._ln(p + "ln_2", x, p + "ln_2")
         f = self.act(rows, self.wt[p + "fc.weight"].shape[0])
-        self._gemm(p + "fc", h, p + "fc", f, act=L.ACT_GELU)
+        self._linear(p + "fc", h, p + "fc", f, act=L.ACT_GELU)
         self.rel(h)
         y = self.act(rows, W)
-        self._gemm(p + "proj", f, p + "proj", y, residual=x.ptr, ldr=W)
+        self._linear(p + "proj", f, p + "proj", y, residual=x.ptr, ldr=W)
         self.rel(f)
         self.rel(x)
         return y
@@ -151,7 +134,7 @@ class ClipTextEngine(_ClipTower):
         if not 0 <= layer_idx < opt.layers:
             raise ValueError("layer_idx")
         self.o, self.B, self.layer_idx = opt, int(B), int(layer_idx)
-        self._init_common(device, taps)
+        self._init_plan(device, taps, groupnorm=False, tuned=False)      # (the towers record on the built-in tile policy)
         self._pack_or_share(sd, donor)
         self._build()
 

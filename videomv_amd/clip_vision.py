@@ -19,7 +19,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing as P
-from .unet_engine import Act
+from .plan_builder import Act
 from .clip_text import _ClipTower
 
 
@@ -71,7 +71,7 @@ class ClipVisionEngine(_ClipTower):
         self.hdp = _padded_head_dim(self.hd)
         self.grid = opt.image_size // opt.patch_size
         self.T = self.grid * self.grid + 1
-        self._init_common(device, taps)
+        self._init_plan(device, taps, groupnorm=False, tuned=False)
         self._pack_or_share(sd, donor)
         self._build()
 

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing as P
-from .unet_engine import Pool, Act
+from .plan_builder import Act, PlanBuilder
 
 
 @dataclasses.dataclass
@@ -98,25 +98,18 @@ def lgm_param_shapes(o: LgmOptions) -> Dict[str, tuple]:
     return d
 
 
-class LgmEngine:
+class LgmEngine(PlanBuilder):
     """Plan for ``LGM.forward_gaussians`` of ``batch`` samples: images [batch * V, 9, H, W] -> gaussians fp32
     [batch * V*S*S, 14] (sample-major).  Everything but the multi-view attention is per image; the attention runs over the
     V*h*w tokens of each sample.  ``packed``: the .wt of another engine of the same model and device (one weight copy)."""
 
+    SPLITK_CAP = 32
+
     def __init__(self, opt: LgmOptions, sd: Dict[str, torch.Tensor], H: int, W: int, device, taps=None, batch: int = 1, packed=None):
-        self.o, self.B, self.H, self.W, self.device = opt, int(batch), H, W, device
+        self.o, self.B, self.H, self.W = opt, int(batch), H, W
         self.V = opt.num_frames * self.B             # images in the plan (rows are image-major)
-        self.pool = Pool(device)
-        self.S = ops.Stream(record=True)
-        self.S.tuner = ops.make_tuner(self)      # measured per-shape (tile, split-K) choices: videomv_amd/tuned_gemm.json
-        self._gnws = torch.empty(4 << 20, dtype=torch.float32, device=device)
-        self._keep = []
-        self.taps = taps
-        if packed is not None:
-            self.wt = packed
-        else:
-            self.wt: Dict[str, torch.Tensor] = {}
-            self._pack(sd)
+        self._init_plan(device, taps)
+        self._take_weights(sd, packed)
         self._build()
 
     # ------------------------------------------------------------------ weights
@@ -174,66 +167,17 @@ class LgmEngine:
         w["final.weight"] = P.pack_linear(sd["conv.weight"].reshape(14, 14), dev)      # LGM.conv (1x1), K padded 14 -> 16
         w["final.bias"] = P.pack_bias(sd["conv.bias"], dev)
 
-    # ------------------------------------------------------------------ helpers
-    def act(self, rows, C, dtype=None):
-        return Act(self.pool.get(rows * C * (4 if dtype == torch.float32 else 2)), rows, C, dtype)
-
-    def rel(self, a):
-        if self.taps is None:
-            self.pool.put(a.buf)
-
-    def _gemm(self, label, M, segs, W, out, ldo=None, bias=None, N=None, **kw):
-        Wt = self.wt[W] if isinstance(W, str) else W
-        if N is None:
-            N = Wt.shape[0]
-        if "ksplit" not in kw and not kw.get("rowstat"):
-            if getattr(self, "_splitk", None) is None:
-                self._splitk = ops.SplitK(self.device if hasattr(self, "device") else self.dev, cap=32)
-            kw["ksplit"], kw["workspace"] = self._splitk.pick(M, N, segs)
-        self.S.gemm(ops.gemm_params(M, N, segs, Wt, out.ptr if isinstance(out, Act) else out,
-                                    ldo if ldo is not None else out.C, bias=bias, **kw), label)
-
-    def _gn(self, label, srcs, hw, key, silu) -> Act:
-        rows = srcs[0].rows
-        C0 = srcs[0].C
-        C1 = srcs[1].C if len(srcs) > 1 else 0
-        y = self.act(rows, C0 + C1)
-        assert ops.gn_partial_floats(rows, hw, C0 + C1) <= self._gnws.numel()
-        self.S.groupnorm(ops.gn_params(srcs[0].ptr, C0, C0, rows, hw, self._gnws, self.wt[key + ".weight"],
-                                       self.wt[key + ".bias"], 1e-5, silu, y.ptr, C0 + C1,
-                                       x1=srcs[1].ptr if C1 else None, ld1=C1, C1=C1), label)
-        return y
-
+    # ------------------------------------------------------------------ blocks
     def _res(self, p, srcs, h, w) -> Act:
-        """srcs = [x] or [x, skip] (channel concat, never materialised)."""
-        T = srcs[0].rows
-        geom = ops.Geom(OH=h, OW=w, IH=h, IW=w)
-        cout = self.wt[p + ".conv1.weight"].shape[0]
-        h0 = self._gn(p + ".norm1", srcs, h * w, p + ".norm1", True)
-        h1 = self.act(T, cout)
-        self._gemm(p + ".conv1", T, ops.conv3x3_segs([(h0.ptr, h0.C, h0.C)]), p + ".conv1.weight", h1,
-                   bias=self.wt[p + ".conv1.bias"], geom=geom)
-        self.rel(h0)
-        h2 = self._gn(p + ".norm2", [h1], h * w, p + ".norm2", True)
-        self.rel(h1)
-        y = self.act(T, cout)
-        segs = ops.conv3x3_segs([(h2.ptr, h2.C, h2.C)])
-        cin = sum(s.C for s in srcs)
-        if cin != cout:
-            segs += ops.linear_segs([(s.ptr, s.C, s.C) for s in srcs])
-            self._gemm(p + ".conv2+shortcut", T, segs, p + ".conv2.weight", y, bias=self.wt[p + ".conv2.bias"], geom=geom)
-        else:           # identity shortcut: (conv2(h) + x) * k = k*conv2(h) + k*x
-            self._gemm(p + ".conv2", T, segs, p + ".conv2.weight", y, bias=self.wt[p + ".conv2.bias"], geom=geom,
-                       residual=srcs[0].ptr, ldr=srcs[0].C, res_scale=self.o.skip_scale)
-        self.rel(h2)
-        return y
+        """srcs = [x] or [x, skip] (channel concat, never materialised).  Identity shortcut: (conv2(h) + x) * k = k*conv2(h) + k*x."""
+        return self._conv_res(p, srcs, h, w, 1e-5, "shortcut", res_scale=self.o.skip_scale)
 
     def _attn(self, p, x: Act, h, w) -> Act:
         o = self.o
         C, T = x.C, x.rows // self.B               # T = V*h*w tokens of one sample
         heads = o.num_heads
         hd = C // heads
-        hn = self._gn(p + ".norm", [x], h * w, p + ".norm", False)
+        hn = self._gn(p + ".norm", [x], h * w, p + ".norm", 1e-5, False)
         qkv = self.act(x.rows, 3 * C)
         self._gemm(p + ".qkv", x.rows, ops.linear_segs([(hn.ptr, C, C)]), p + ".qkv", qkv)
         ao = self.act(x.rows, C)
@@ -292,12 +236,7 @@ class LgmEngine:
                 x = y
                 xss.append((x, h, w))
             if i != nd - 1:
-                oh, ow = (h + 1) // 2, (w + 1) // 2
-                p = f"down_blocks.{i}.downsample"
-                y = self.act(V * oh * ow, x.C)
-                self._gemm(p, y.rows, ops.conv3x3_segs([(x.ptr, x.C, x.C)]), p + ".weight", y, bias=self.wt[p + ".bias"],
-                           geom=ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=2))
-                x, h, w = y, oh, ow
+                x, h, w = self._conv_down(f"down_blocks.{i}.downsample", x, h, w)
                 xss.append((x, h, w))
             if self.taps is not None:
                 self.taps[f"down_blocks.{i}"] = (x, h, w)
@@ -324,17 +263,14 @@ class LgmEngine:
                     y = y2
                 x = y
             if i != nu - 1:
-                p = f"up_blocks.{i}.upsample"
-                y = self.act(V * 4 * h * w, x.C)
-                self._gemm(p, y.rows, ops.conv3x3_segs([(x.ptr, x.C, x.C)]), p + ".weight", y, bias=self.wt[p + ".bias"],
-                           geom=ops.Geom(OH=2 * h, OW=2 * w, IH=h, IW=w, ups=1))
+                y, oh, ow = self._conv_up(f"up_blocks.{i}.upsample", x, h, w)
                 self.rel(x)
-                x, h, w = y, 2 * h, 2 * w
+                x, h, w = y, oh, ow
             if self.taps is not None:
                 self.taps[f"up_blocks.{i}"] = (x, h, w)
         for leftover, _, _ in xss:            # the 'big' U-Net is asymmetric (5 decoder levels for 6 encoder levels): the
             self.rel(leftover)                # shallowest skips are simply unused, as in the reference (core/unet.py:306-310)
-        hn = self._gn("norm_out", [x], h * w, "norm_out", True)
+        hn = self._gn("norm_out", [x], h * w, "norm_out", 1e-5, True)
         self.rel(x)
         T = V * h * w
         self.S_out, self.T_out = h, T

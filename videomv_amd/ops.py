@@ -229,8 +229,8 @@ def make_tuner(owner):
     """ops.Stream hook (Stream.tuner) of an engine: applies the measured (tile, split-K) choice of tuned_gemm.json to a GEMM about to be
     recorded — auto tiles only.  The forced choice is VALIDATED here (vmv_gemm_validate: the launch's whole host side without the
     device); an entry the library would refuse — a stale VMV_TUNED_CACHE / VMV_TUNED_FILE, a tile whose eligibility changed — is
-    dropped with one warning and the built-in policy stands, instead of VMV_EINVAL on the first replay.  `owner`
-    provides .device (or .dev) and keeps the split-K slab (._splitk) and the hit count (.n_tuned)."""
+    dropped with one warning and the built-in policy stands, instead of VMV_EINVAL on the first replay.  `owner` (a
+    plan_builder.PlanBuilder) holds the split-K slab (._splitk) and the hit counts (.n_tuned, .n_ruled, .n_stale)."""
     def tune(p):
         if p.tile != L.TILE_AUTO or p.wgroup_rows or p.epilogue == L.EPI_TATTN:      # (the fused q|k|v + attention has ONE kernel)
             return
@@ -246,8 +246,6 @@ def make_tuner(owner):
         ks = int(ent.get("ksplit", 0))
         keep = (p.tile, p.ksplit, p.workspace)
         if ks > 1:
-            if getattr(owner, "_splitk", None) is None:
-                owner._splitk = SplitK(owner.device if hasattr(owner, "device") else owner.dev, cap=8)
             p.workspace = owner._splitk.workspace(ks * p.M * p.N * 4).data_ptr()
         p.ksplit = ks if ks > 1 else 0
         p.tile = int(ent.get("tile", 0))

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing as P
-
+from .plan_builder import Act, PlanBuilder, Pool  # noqa: F401  (Pool / Act: imported from here by the other engines and by callers)
 
 
 # --------------------------------------------------------------------------------------------- architecture
@@ -148,49 +148,8 @@ def param_shapes(cfg) -> "Dict[str, tuple]":
     return dict(s)
 
 
-# --------------------------------------------------------------------------------------------- device memory
-class Pool:
-    """Size-bucketed reuse of device buffers.  All launches are stream-ordered on ONE stream, so a buffer can
-    be handed to a later op as soon as its last consumer has been *recorded*."""
-
-    def __init__(self, device):
-        self.device = device
-        self.free: Dict[int, List[torch.Tensor]] = {}
-        self.all: List[torch.Tensor] = []
-        self.bytes = 0
-
-    def get(self, nbytes: int) -> torch.Tensor:
-        nbytes = (int(nbytes) + 255) // 256 * 256
-        lst = self.free.get(nbytes)
-        if lst:
-            return lst.pop()
-        t = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.all.append(t)
-        self.bytes += nbytes
-        return t
-
-    def put(self, t: torch.Tensor):
-        self.free.setdefault(t.numel(), []).append(t)
-
-
-class Act:
-    """A [rows, C] activation living in a pooled buffer."""
-    __slots__ = ("buf", "rows", "C", "dtype")
-
-    def __init__(self, buf, rows, C, dtype=None):
-        self.buf, self.rows, self.C, self.dtype = buf, rows, C, dtype or L.elem()
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def tensor(self) -> torch.Tensor:
-        esz = 4 if self.dtype == torch.float32 else 2
-        return self.buf[: self.rows * self.C * esz].view(self.dtype).view(self.rows, self.C)
-
-
 # --------------------------------------------------------------------------------------------- the engine
-class UNetEngine:
+class UNetEngine(PlanBuilder):
     def __init__(self, cfg: dict, weights: Dict[str, torch.Tensor], B: int, F: int, H: int, W: int, L_ctx: int,
                  device, n_t: int = 1, taps: Optional[dict] = None, comm=None, share_prefix: bool = False,
                  packed: Optional[dict] = None, eps_out: Optional[torch.Tensor] = None):
@@ -218,23 +177,13 @@ class UNetEngine:
         self.cfg, self.B, self.F, self.H, self.W, self.L = cfg, B, F, H, W, L_ctx
         self.B_ctx = B               # number of context (text) branches; self.B drops to 1 while a shared prefix is recorded
         self.device = device
-        self.breaks = []            # (op index, callable): collectives issued by Python before that recorded op (no VmvComm handle)
-        self.n_comm_ops, self.comm_bytes_in = 0, 0   # collectives recorded INTO the plan (VMV_OP_COMM); bytes received from peers per replay
-        self.pool = Pool(device)
-        self.S = ops.Stream(record=True)
-        self.Sctx = ops.Stream(record=True)      # step-invariant launches: K / V of the text context (run by context_updated())
-        self._keepalive = []
-        self._splitk = None
-        self._gnws = torch.empty(4 << 20, dtype=torch.float32, device=device)
         # pre-folded statistics of the all-frame norms: [nstat][32][2] per rank (+ the gathered [R][nstat][32][2]), tickets
         # two buffers used alternately by consecutive all-frame norms (the apply pass of one clears the other's)
         # (records of ops.GN_REC int64 per (stat group, channel group): two-limb sums of x - pilot, sums of squares, the pilot)
         # (every all-frame norm of an engine has nstat = B stat groups — one per branch: B x GN_TOT int64 per buffer)
         self._gn_tot2 = torch.zeros(2, B * ops.GN_TOT, dtype=torch.int64, device=device)
         self._gn_zero = torch.zeros(2, B * ops.GN_TOT, dtype=torch.int64, device=device)   # source of the plan's own clearing copy
-        self._gn_tot_k = 0
         self._gn_tot_all = torch.zeros(B * ops.GN_TOT * self.R, dtype=torch.int64, device=device) if comm is not None else None
-        self.taps = taps            # optional dict: prefix -> Act (buffers are then never recycled)
         self.n_t = n_t
         self.dim = cfg["dim"]
         self.E = self.dim * 4
@@ -256,7 +205,7 @@ class UNetEngine:
         # VMV_FP_TEMPORAL (frame-parallel plans): "switch" (default) = the TemporalTransformer runs on the pixel-major shard between two
         # all-to-all layout switches; "kv_gather" = BASELINE's north-star form — frames stay sharded, ONE all-gather of [K | V] before
         # each temporal attention (B = 1 plans, i.e. the branch-pipelined / CFG-parallel modes; 16x the bytes of the switches)
-        self.use_graph, self._replays, self.graph_nodes = os.environ.get("VMV_GRAPH", "0") == "1", 0, 0
+        self.use_graph = os.environ.get("VMV_GRAPH", "0") == "1"
         self.fp_temporal = os.environ.get("VMV_FP_TEMPORAL", "switch")
         if self.fp_temporal not in ("switch", "kv_gather"):
             raise ValueError("VMV_FP_TEMPORAL must be 'switch' or 'kv_gather'")
@@ -268,13 +217,11 @@ class UNetEngine:
                     setattr(self, k, v)
         else:
             self._pack(weights)
+        self.wt = self.w            # (PlanBuilder's name of the packed-weight dict: the same object)
         self.packed = dict(fold_ln=self.fold_ln, device=str(device), w=self.w, has_cam=self.has_cam, has_fps=self.has_fps,
                            emb_off=self.emb_off, emb_total=self.emb_total, out_pad=self.out_pad)
         self._eps_out = eps_out
-        self.n_tuned, self.n_ruled, self.n_stale = 0, 0, 0      # launches forced by the table / by ops.fill_rule / table entries the library refused
-        self.S.tuner = ops.make_tuner(self)      # measured per-shape (tile, split-K) choices: videomv_amd/tuned_gemm.json
-        self._static_inputs()
-        self._build()
+        self._record(taps)
         # VMV_AUTOTUNE=1: a shape the tile table does not cover tunes itself once (autotune.py) and the plan is recorded again with
         # the winners — from a clean slate: new streams, pool and accumulators (the packed weights are kept)
         if os.environ.get("VMV_AUTOTUNE", "0") == "1" and taps is None and str(device).startswith("cuda"):
@@ -282,21 +229,22 @@ class UNetEngine:
             if autotune.autotune_engine(self, tag=f"B{B} F{self.Fg} {H}x{W} world{self.R}") > 0:
                 self._rerecord()
 
-    def _rerecord(self):
-        """Record the plan again (the tile table changed): fresh streams / pool / accumulators, same packed weights and geometry."""
-        dev = self.device
+    def _record(self, taps):
+        """Record the plan from a clean slate: streams, pool, split-K slab, tile-table counters, accumulators and static buffers."""
+        self._init_plan(self.device, taps)
+        self.Sctx = ops.Stream(record=True)      # step-invariant launches: K / V of the text context (run by context_updated())
         self.B = self.B_ctx
-        self.breaks, self.n_comm_ops, self.comm_bytes_in = [], 0, 0
-        self.pool = Pool(dev)
-        self.S = ops.Stream(record=True)
-        self.Sctx = ops.Stream(record=True)
-        self._keepalive, self._splitk = [], None
+        self.breaks = []            # (op index, callable): collectives issued by Python before that recorded op (no VmvComm handle)
+        self.n_comm_ops, self.comm_bytes_in = 0, 0   # collectives recorded INTO the plan (VMV_OP_COMM); bytes received from peers per replay
         self._gn_tot2.zero_()
         self._gn_tot_k = 0
-        self._replays, self.graph_nodes, self.n_tuned, self.n_ruled, self.n_stale = 0, 0, 0, 0, 0
-        self.S.tuner = ops.make_tuner(self)
+        self._replays, self.graph_nodes = 0, 0
         self._static_inputs()
         self._build()
+
+    def _rerecord(self):
+        """Record the plan again (the tile table changed): same packed weights and geometry."""
+        self._record(self.taps)
 
     # ------------------------------------------------------------------ weights
     def _pack(self, sd):
@@ -439,73 +387,55 @@ class UNetEngine:
         self.extra_emb = None        # optional fp32 [n_t, E] added to the time embedding (I2VGen: fps_embedding)
 
     # ------------------------------------------------------------------ helpers
-    def act(self, rows, C, dtype=None) -> Act:
-        esz = 4 if dtype == torch.float32 else 2
-        return Act(self.pool.get(rows * C * esz), rows, C, dtype)
-
-    def release(self, a: Act):
-        if self.taps is None:
-            self.pool.put(a.buf)
-
-    def _gemm(self, label, M, N, segs, wkey, out: Act, bias=None, geom=None, stream=None, **kw):
-        """N is informational: the launch always covers every (4-padded) row of the packed weight."""
-        W = self.w[wkey]
-        ks, ws = (0, None) if kw.get("rowstat") else self._ksplit(M, W.shape[0], segs)      # (folded-LN GEMMs: no split-K)
-        p = ops.gemm_params(M, W.shape[0], segs, W, out.ptr, out.C, bias=bias, geom=geom, ksplit=ks, workspace=ws, **kw)
-        (stream or self.S).gemm(p, label)
-
-    def _up_conv(self, label, M, xin: Act, out: Act, geom):
+    def _conv_up(self, p, x: Act, h, w):
         """Upsample (nearest x2 -> 3x3 convolution, util.py:595-606): ONE launch — four 2x2 phase convolutions over the source pixels with
         the pre-summed weights (K = 4 C; vmv.h VmvGemmParams.phased) where the library prefers that form (vmv_gemm_up4_ok), else the
         nine-tap gather over the up-sampled image."""
-        W4 = self.w[label + ".weight.up4"]
-        p = ops.gemm_params(M, W4.shape[0] // 4, ops.up4_segs(xin.ptr, xin.C, xin.C), W4, out.ptr, out.C, bias=self.w[label + ".bias"],
-                            geom=geom, phased=True)
-        if self.S.lib.vmv_gemm_up4_ok(C.byref(p)):
-            self.S.gemm(p, label)
-        else:
-            self._gemm(label, M, out.C, ops.conv3x3_segs([(xin.ptr, xin.C, xin.C)]), label + ".weight", out, bias=self.w[label + ".bias"], geom=geom)
+        y = self.act(4 * x.rows, x.C)
+        W4 = self.w[p + ".weight.up4"]
+        gp = ops.gemm_params(y.rows, W4.shape[0] // 4, ops.up4_segs(x.ptr, x.C, x.C), W4, y.ptr, y.C, bias=self.w[p + ".bias"],
+                             geom=ops.Geom(OH=2 * h, OW=2 * w, IH=h, IW=w, stride=1, ups=1), phased=True)
+        if not self.S.lib.vmv_gemm_up4_ok(C.byref(gp)):
+            return super()._conv_up(p, x, h, w, out=y)
+        self.S.gemm(gp, p)
+        return y, 2 * h, 2 * w
 
-    def _ksplit(self, M, N, segs):
-        """Split K when the tile grid cannot fill 256 CUs and the reduction is long (small-spatial levels)."""
-        if self._splitk is None:
-            self._splitk = ops.SplitK(self.device, cap=8)
-        return self._splitk.pick(M, N, segs)
-
-    def _gn(self, label, srcs, rows, rows_per_stat, wkey, eps, silu, all_frames=False) -> Act:
+    def _gn(self, label, srcs, rows_per_stat, wkey, eps, silu, all_frames=False) -> Act:
         """all_frames: a 5-D norm whose statistics span every frame.  Frame-parallel: the input is the
         pixel-major shard, so each rank sums its HW/R pixels of all frames, the per-chunk partial sums are
         all-gathered, and every rank folds all R shards in the same order (bitwise identical statistics)."""
-        C0 = srcs[0].C
-        C1 = srcs[1].C if len(srcs) > 1 else 0
-        C = C0 + C1
-        y = self.act(rows, C)
-        nfl = ops.gn_partial_floats(rows, rows_per_stat, C)
-        assert nfl <= self._gnws.numel()
-        nstat = rows // rows_per_stat
-        base = dict(x1=srcs[1].ptr if C1 else None, ld1=srcs[1].C if C1 else 0, C1=C1)
-        args = (srcs[0].ptr, srcs[0].C, C0, rows, rows_per_stat, self._gnws, self.w[wkey + ".weight"], self.w[wkey + ".bias"],
-                eps, silu, y.ptr, C)
         if not all_frames:      # (one fused launch when the stat group fits on chip — the small levels — else stats + apply)
-            self.S.groupnorm(ops.gn_params(*args, **base), label)
-            return y
-        fused = 0 if self.comm is not None else ops.gn_fused_cols(rows_per_stat, C)
+            return super()._gn(label, srcs, rows_per_stat, wkey, eps, silu)
+        x, rows, Cc = srcs[0], srcs[0].rows, srcs[0].C
+        y = self.act(rows, Cc)
+        assert ops.gn_partial_floats(rows, rows_per_stat, Cc) <= self._gnws.numel()
+        params = lambda **kw: ops.gn_params(x.ptr, Cc, Cc, rows, rows_per_stat, self._gnws, self.w[wkey + ".weight"], self.w[wkey + ".bias"],
+                                            eps, silu, y.ptr, Cc, **kw)
+        fused = 0 if self.comm is not None else ops.gn_fused_cols(rows_per_stat, Cc)
         if fused:               # all-frame norm whose stat group still fits on chip (L3 / middle block)
-            self.S.groupnorm_fused(ops.gn_params(*args, **base), fused, label)
-            return y
-        # all-frame norm: up to 256 chunks per stat group -> a one-block fold after the stats folds them once (pre-folded totals)
+            self.S.groupnorm_fused(params(), fused, label)
+        else:                   # up to 256 chunks per stat group -> a one-block fold after the stats folds them once (pre-folded totals)
+            self._gn_all_frames(label, rows // rows_per_stat, params, self.S.groupnorm_apply)
+        return y
+
+    def _gn_all_frames(self, label, nstat, params, second):
+        """The two launches of a norm whose statistics span all frames: the statistics pass adds into the integer totals of one of the
+        two accumulator buffers (a ticket: consecutive norms alternate), `second` (S.groupnorm_apply | S.groupnorm_table) folds them and
+        clears the OTHER buffer for the next norm.  params(**totals arguments) -> the norm's gn_params.  Frame-parallel plans all-gather
+        the ranks' totals in between and fold all R shards."""
         assert nstat <= self.B_ctx
         tot, nxt = self._gn_tot2[self._gn_tot_k & 1], self._gn_tot2[(self._gn_tot_k + 1) & 1]
         self._gn_tot_k += 1
         clr = dict(totals_clear=nxt, clear_count=nstat * ops.GN_TOT)      # (every all-frame norm of an engine has nstat = B)
         if self.comm is None:
-            self.S.groupnorm(ops.gn_params(*args, totals=tot, **clr, **base), label)
-            return y
-        self.S.groupnorm_stats(ops.gn_params(*args, totals=tot, **base), label)
+            gnp = params(totals=tot, **clr)
+            self.S.groupnorm_stats(gnp, label)
+            second(gnp, label)
+            return
+        self.S.groupnorm_stats(params(totals=tot), label)
         loc, allr = tot[: nstat * ops.GN_TOT], self._gn_tot_all[: nstat * ops.GN_TOT * self.R]
         self._collective(L.COMM_ALL_GATHER, allr, loc, label + ".totals.gather")
-        self.S.groupnorm_apply(ops.gn_params(*args, totals=self._gn_tot_all, fold_ranks=self.R, **clr, **base), label)
-        return y
+        second(params(totals=self._gn_tot_all, fold_ranks=self.R, **clr), label)
 
     def _gn_folded_proj_in(self, p, x: Act, T, rps, out: Act, all_frames) -> bool:
         """SpatialTransformer / TemporalTransformer head (util.py:354-360, 1043-1050): GroupNorm -> proj_in with the norm's apply
@@ -525,17 +455,15 @@ class UNetEngine:
             self.release(tab)
             return False
         label = p + ".norm"
-        args = (x.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{p}.norm.weight"], self.w[f"{p}.norm.bias"], 1e-6, False, tab.ptr, Cc)
+        params = lambda **kw: ops.gn_params(x.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{p}.norm.weight"], self.w[f"{p}.norm.bias"], 1e-6, False,
+                                            tab.ptr, Cc, **kw)
         assert ops.gn_partial_floats(T, rps, Cc) <= self._gnws.numel()
         if all_frames:          # long stat groups: integer totals (as _gn)
-            assert nstat <= self.B_ctx
-            tot, nxt = self._gn_tot2[self._gn_tot_k & 1], self._gn_tot2[(self._gn_tot_k + 1) & 1]
-            self._gn_tot_k += 1
-            gnp = ops.gn_params(*args, totals=tot, totals_clear=nxt, clear_count=nstat * ops.GN_TOT)
+            self._gn_all_frames(label, nstat, params, self.S.groupnorm_table)
         else:
-            gnp = ops.gn_params(*args)
-        self.S.groupnorm_stats(gnp, label)
-        self.S.groupnorm_table(gnp, label)
+            gnp = params()
+            self.S.groupnorm_stats(gnp, label)
+            self.S.groupnorm_table(gnp, label)
         self.S.gemm(gp, p + ".proj_in")
         self.release(tab)
         return True
@@ -564,21 +492,10 @@ class UNetEngine:
         if not (trs or self.S.lib.vmv_gemm_tfr_ok(C.byref(gp))):
             self.release(tab)
             return False
-        label = q + ".gn"
-        assert nstat <= self.B_ctx and ops.gn_partial_floats(T, rps, Cc) <= self._gnws.numel()
-        args = (cur.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{q}.0.weight"], self.w[f"{q}.0.bias"], 1e-5, False, tab.ptr, Cc)
-        tot, nxt = self._gn_tot2[self._gn_tot_k & 1], self._gn_tot2[(self._gn_tot_k + 1) & 1]
-        self._gn_tot_k += 1
-        clr = dict(totals_clear=nxt, clear_count=nstat * ops.GN_TOT)
-        if self.comm is None:
-            gnp = ops.gn_params(*args, totals=tot, **clr)
-            self.S.groupnorm_stats(gnp, label)
-            self.S.groupnorm_table(gnp, label)
-        else:
-            self.S.groupnorm_stats(ops.gn_params(*args, totals=tot), label)
-            loc, allr = tot[: nstat * ops.GN_TOT], self._gn_tot_all[: nstat * ops.GN_TOT * self.R]
-            self._collective(L.COMM_ALL_GATHER, allr, loc, label + ".totals.gather")
-            self.S.groupnorm_table(ops.gn_params(*args, totals=self._gn_tot_all, fold_ranks=self.R, **clr), label)
+        assert ops.gn_partial_floats(T, rps, Cc) <= self._gnws.numel()
+        params = lambda **kw: ops.gn_params(cur.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{q}.0.weight"], self.w[f"{q}.0.bias"], 1e-5, False,
+                                            tab.ptr, Cc, **kw)
+        self._gn_all_frames(q + ".gn", nstat, params, self.S.groupnorm_table)
         self.S.gemm(gp, q)
         self.release(tab)
         return True
@@ -650,12 +567,12 @@ class UNetEngine:
         self.release(recv)
         return y
 
-    def _ln_linear(self, label, x: Act, nkey, N, wkey, out: Act, bias=None, **kw):
+    def _ln_linear(self, label, x: Act, nkey, wkey, out: Act, bias=None, **kw):
         """out = Linear(LayerNorm(x)).  Folded: row statistics (mean, rstd) + one GEMM on the raw rows whose epilogue
         applies them (weights pre-multiplied by gamma, beta folded into the bias: packing.fold_layernorm)."""
         if not self.fold_ln:
             ln = self._ln(label + ".ln", x, nkey)
-            self._gemm(label, x.rows, N, ops.linear_segs([(ln.ptr, ln.C, ln.C)]), wkey, out, bias=bias, **kw)
+            self._gemm(label, x.rows, ops.linear_segs([(ln.ptr, ln.C, ln.C)]), wkey, out, bias=bias, **kw)
             self.release(ln)
             return
         base = wkey[:-len(".weight")] if wkey.endswith(".weight") else wkey
@@ -671,7 +588,7 @@ class UNetEngine:
             return
         st = self.act(x.rows, 2, dtype=torch.float32)
         self.S.layernorm(ops.ln_params(x.ptr, x.C, None, 0, None, None, x.rows, x.C, 1e-5, stats_out=st.ptr), label + ".lnstat")
-        self._gemm(label, x.rows, N, segs, base + ".ln.weight", out,
+        self._gemm(label, x.rows, segs, base + ".ln.weight", out,
                    bias=self.w[base + ".ln.bias"], rowstat=st.ptr, colsum=self.w[base + ".ln.colsum"], **kw)
         self.release(st)
 
@@ -690,27 +607,10 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ blocks
     def _res_block(self, p, m, srcs: List[Act], h, w) -> Act:
-        B, F = self.B, self.F
-        T = B * F * h * w
-        cout = m["cout"]
-        geom = ops.Geom(OH=h, OW=w, IH=h, IW=w, stride=1, ups=0)
-        h0 = self._gn(p + ".gn1", srcs, T, h * w, f"{p}.in_layers.0", 1e-5, True)
-        h1 = self.act(T, cout)
-        self._gemm(p + ".conv1", T, cout, ops.conv3x3_segs([(h0.ptr, h0.C, h0.C)]), f"{p}.in_layers.2.weight", h1,
-                   bias=self.w[f"{p}.in_layers.2.bias"], geom=geom,
-                   rowvec=self.emb_out.data_ptr() + 4 * self.emb_off[p], rowvec_div=h * w, rowvec_ld=self.emb_total)
-        self.release(h0)
-        h2 = self._gn(p + ".gn2", [h1], T, h * w, f"{p}.out_layers.0", 1e-5, True)
-        self.release(h1)
-        h3 = self.act(T, cout)
-        segs = ops.conv3x3_segs([(h2.ptr, h2.C, h2.C)])
-        if m["cin"] != cout:
-            segs += ops.linear_segs([(s.ptr, s.C, s.C) for s in srcs])
-            self._gemm(p + ".conv2+skip", T, cout, segs, f"{p}.conv2.weight", h3, bias=self.w[f"{p}.conv2.bias"], geom=geom)
-        else:
-            self._gemm(p + ".conv2", T, cout, segs, f"{p}.conv2.weight", h3, bias=self.w[f"{p}.conv2.bias"], geom=geom,
-                       residual=srcs[0].ptr, ldr=srcs[0].C)
-        self.release(h2)
+        F, cout = self.F, m["cout"]
+        h3 = self._conv_res(p, srcs, h, w, 1e-5, "skip", keys=("gn1", "in_layers.0", "in_layers.2", "gn2", "out_layers.0"),
+                            conv1_kw=dict(rowvec=self.emb_out.data_ptr() + 4 * self.emb_off[p], rowvec_div=h * w, rowvec_ld=self.emb_total))
+        T = h3.rows
         # temporal conv block: 4 x [GN over all frames -> SiLU -> (3,1,1) conv], + identity.  Frame-parallel: pixel-local,
         # so it runs on the pixel-major shard (all Fg frames of HW/R pixels) between two layout switches.
         if self.comm is not None:
@@ -722,8 +622,8 @@ class UNetEngine:
             nxt = self.act(T, cout)
             last = i == 3
             if not self._tconv_folded(q, cur, T, F * h * w, nxt, tg, residual=h3.ptr if last else None, ldr=h3.C if last else 0):
-                g = self._gn(q + ".gn", [cur], T, F * h * w, f"{q}.0", 1e-5, True, all_frames=True)
-                self._gemm(q, T, cout, ops.temporal_segs(g.ptr, g.C, g.C), f"{q}.weight", nxt, bias=self.w[f"{q}.bias"],
+                g = self._gn(q + ".gn", [cur], F * h * w, f"{q}.0", 1e-5, True, all_frames=True)
+                self._gemm(q, T, ops.temporal_segs(g.ptr, g.C, g.C), f"{q}.weight", nxt, bias=self.w[f"{q}.bias"],
                            geom=tg, residual=h3.ptr if last else None, ldr=h3.C if last else 0)
                 self.release(g)
             if cur is not h3:
@@ -781,16 +681,20 @@ class UNetEngine:
                 self.release(ln)
             return ao
 
+        def attn_out(tag, ao: Act, x: Act) -> Act:
+            """x + to_out(ao); ao is released."""
+            y = self.act(T, inner)
+            self._gemm(f"{p}.{tag}.out", T, ops.linear_segs([(ao.ptr, ao.C, ao.C)]), f"{p}.{tag}.to_out.0.weight", y,
+                       bias=self.w[f"{p}.{tag}.to_out.0.bias"], residual=x.ptr, ldr=x.C)
+            self.release(ao)
+            return y
+
         def self_attn(tag, x: Act, normkey) -> Act:
             ao = fused_qkv_attn(tag, x, normkey)
             if ao is not None:
-                y = self.act(T, inner)
-                self._gemm(f"{p}.{tag}.out", T, inner, ops.linear_segs([(ao.ptr, ao.C, ao.C)]), f"{p}.{tag}.to_out.0.weight", y,
-                           bias=self.w[f"{p}.{tag}.to_out.0.bias"], residual=x.ptr, ldr=x.C)
-                self.release(ao)
-                return y
+                return attn_out(tag, ao, x)
             qkv = self.act(T, 3 * inner)
-            self._ln_linear(f"{p}.{tag}.qkv", x, f"{p}.{normkey}", 3 * inner, f"{p}.{tag}.qkv", qkv)
+            self._ln_linear(f"{p}.{tag}.qkv", x, f"{p}.{normkey}", f"{p}.{tag}.qkv", qkv)
             ao = self.act(T, inner)
             ld = 3 * inner
             if kv_gather:
@@ -815,35 +719,26 @@ class UNetEngine:
                                                  maps(ld), maps(ld), maps(ld), maps(inner), n_outer, heads, Nq, Nq, scale),
                                  f"{p}.{tag}.attn")
             self.release(qkv)
-            y = self.act(T, inner)
-            self._gemm(f"{p}.{tag}.out", T, inner, ops.linear_segs([(ao.ptr, ao.C, ao.C)]), f"{p}.{tag}.to_out.0.weight", y,
-                       bias=self.w[f"{p}.{tag}.to_out.0.bias"], residual=x.ptr, ldr=x.C)
-            self.release(ao)
-            return y
+            return attn_out(tag, ao, x)
 
         def cross_attn(tag, x: Act, normkey) -> Act:
             q = self.act(T, inner)
-            self._ln_linear(f"{p}.{tag}.q", x, f"{p}.{normkey}", inner, f"{p}.{tag}.q", q)
+            self._ln_linear(f"{p}.{tag}.q", x, f"{p}.{normkey}", f"{p}.{tag}.q", q)
             Lc = self.L
             # K / V of the text tokens do not depend on x_t or t: computed once per sample (context_updated()), on B*L rows
             # — the reference recomputes them on 24 copies of the tokens in every forward (unet_t2v.py:346, util.py:224-225)
             Bc = self.B_ctx
             kvt = torch.empty(Bc * Lc, 2 * inner, dtype=L.elem(), device=self.device)
-            self._keepalive.append(kvt)
+            self._keep.append(kvt)
             kv = Act(kvt.view(torch.uint8).view(-1), Bc * Lc, 2 * inner)
             cd = self.ctx_rows.shape[1]
-            self._gemm(f"{p}.{tag}.kv", Bc * Lc, 2 * inner, ops.linear_segs([(self.ctx_rows.data_ptr(), cd, cd)]),
-                       f"{p}.{tag}.kv", kv, stream=self.Sctx)
+            self._gemm(f"{p}.{tag}.kv", Bc * Lc, ops.linear_segs([(self.ctx_rows.data_ptr(), cd, cd)]), f"{p}.{tag}.kv", kv, stream=self.Sctx)
             ao = self.act(T, inner)
             kvm = ops.seq_map(Lc * 2 * inner, 0, 2 * inner, inner=1)
             self.S.attention(ops.attn_params(q.ptr, kv.ptr, kv.ptr + 2 * inner, ao.ptr, maps(inner), kvm, kvm, maps(inner),
                                              n_outer, heads, Nq, Lc, scale, kv_div=F), f"{p}.{tag}.attn")
             self.release(q)
-            y = self.act(T, inner)
-            self._gemm(f"{p}.{tag}.out", T, inner, ops.linear_segs([(ao.ptr, ao.C, ao.C)]), f"{p}.{tag}.to_out.0.weight", y,
-                       bias=self.w[f"{p}.{tag}.to_out.0.bias"], residual=x.ptr, ldr=x.C)
-            self.release(ao)
-            return y
+            return attn_out(tag, ao, x)
 
         if phase == "post":
             a1 = a
@@ -865,9 +760,9 @@ class UNetEngine:
                 self.release(a2)
                 return a3
         ff = self.act(T, 4 * inner)
-        self._ln_linear(f"{p}.ff.geglu", a2, f"{p}.norm3", 8 * inner, f"{p}.ff.net.0.proj.weight", ff,
+        self._ln_linear(f"{p}.ff.geglu", a2, f"{p}.norm3", f"{p}.ff.net.0.proj.weight", ff,
                         bias=self.w[f"{p}.ff.net.0.proj.bias"], epilogue=L.EPI_GEGLU)
-        self._gemm(f"{p}.ff.down", T, inner, ops.linear_segs([(ff.ptr, ff.C, ff.C)]), f"{p}.ff.net.2.weight", a3,
+        self._gemm(f"{p}.ff.down", T, ops.linear_segs([(ff.ptr, ff.C, ff.C)]), f"{p}.ff.net.2.weight", a3,
                    bias=self.w[f"{p}.ff.net.2.bias"], residual=a2.ptr, ldr=a2.C)
         self.release(ff); self.release(a2)
         return a3
@@ -889,8 +784,8 @@ class UNetEngine:
         rps = (F * h * w) if temporal else (h * w)
         a = self.act(T, inner)
         if not self._gn_folded_proj_in(p, x, T, rps, a, temporal):
-            n0 = self._gn(p + ".norm", [x], T, rps, f"{p}.norm", 1e-6, False, all_frames=temporal)
-            self._gemm(p + ".proj_in", T, inner, ops.linear_segs([(n0.ptr, n0.C, n0.C)]), f"{p}.proj_in.weight", a,
+            n0 = self._gn(p + ".norm", [x], rps, f"{p}.norm", 1e-6, False, all_frames=temporal)
+            self._gemm(p + ".proj_in", T, ops.linear_segs([(n0.ptr, n0.C, n0.C)]), f"{p}.proj_in.weight", a,
                        bias=self.w[f"{p}.proj_in.bias"])
             self.release(n0)
         if cut:
@@ -907,7 +802,7 @@ class UNetEngine:
             a3 = self._tblock(f"{p}.transformer_blocks.0", a, m["heads"], temporal, h, w, cross_ctx=not temporal, kv_gather=kvg)
             self.release(a)
         y = self.act(T, C)
-        self._gemm(p + ".proj_out", T, C, ops.linear_segs([(a3.ptr, a3.C, a3.C)]), f"{p}.proj_out.weight", y,
+        self._gemm(p + ".proj_out", T, ops.linear_segs([(a3.ptr, a3.C, a3.C)]), f"{p}.proj_out.weight", y,
                    bias=self.w[f"{p}.proj_out.bias"], residual=x.ptr, ldr=x.C)
         self.release(a3)
         if cut:
@@ -926,27 +821,16 @@ class UNetEngine:
             if kind == "conv_in":
                 T_in = self.B * self.F * h * w          # (one branch's rows while the shared prefix is recorded)
                 y = self.act(T_in, m["cout"])
-                self._gemm(p, T_in, m["cout"], ops.conv3x3_segs([(self.x_rows.data_ptr(), self.cin_pad, self.cin_pad)]),
+                self._gemm(p, T_in, ops.conv3x3_segs([(self.x_rows.data_ptr(), self.cin_pad, self.cin_pad)]),
                            p + ".weight", y, bias=self.w[p + ".bias"], geom=ops.Geom(OH=h, OW=w, IH=h, IW=w))
             elif kind == "res":
                 y = self._res_block(p, m, ins, h, w)
             elif kind in ("st", "tt"):
                 y = self._transformer(kind, p, m, ins[0], h, w, cut=(kind == "st" and self.B != self.B_ctx))
             elif kind == "down":
-                xin = ins[0]
-                oh, ow = (h + 1) // 2, (w + 1) // 2
-                T = self.B * self.F * oh * ow
-                y = self.act(T, m["c"])
-                self._gemm(p, T, m["c"], ops.conv3x3_segs([(xin.ptr, xin.C, xin.C)]), p + ".weight", y,
-                           bias=self.w[p + ".bias"], geom=ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=2))
-                h, w = oh, ow
+                y, h, w = self._conv_down(p, ins[0], h, w)
             elif kind == "up":
-                xin = ins[0]
-                oh, ow = h * 2, w * 2
-                T = self.B * self.F * oh * ow
-                y = self.act(T, m["c"])
-                self._up_conv(p, T, xin, y, ops.Geom(OH=oh, OW=ow, IH=h, IW=w, stride=1, ups=1))
-                h, w = oh, ow
+                y, h, w = self._conv_up(p, ins[0], h, w)
             else:
                 raise ValueError(kind)
             if x is not None:
@@ -969,7 +853,7 @@ class UNetEngine:
         self.n_emb_ops_start = S.nops
         e = Act(self.emb_silu.view(torch.uint8).view(-1), B * F, self.E)
         eo = Act(self.emb_out.view(torch.uint8).view(-1), B * F, self.emb_total, torch.float32)
-        self._gemm("emb_all", B * F, self.emb_total, ops.linear_segs([(e.ptr, e.C, e.C)]), "emb_all.weight", eo,
+        self._gemm("emb_all", B * F, ops.linear_segs([(e.ptr, e.C, e.C)]), "emb_all.weight", eo,
                    bias=self.w["emb_all.bias"], out_fp32=True)
         h, w = self.H, self.W
         xs = []
@@ -1008,10 +892,10 @@ class UNetEngine:
             if self.taps is not None:
                 self.taps[blk[0][1]] = (x, h, w)
         T = self.T0
-        hn = self._gn("out.gn", [x], T, h * w, "out.0", 1e-5, True)
+        hn = self._gn("out.gn", [x], h * w, "out.0", 1e-5, True)
         self.release(x)
         eps = Act(self.eps_rows.view(torch.uint8).view(-1), T, self.out_pad, torch.float32)
-        self._gemm("out.conv", T, self.out_pad, ops.conv3x3_segs([(hn.ptr, hn.C, hn.C)]), "out.2.weight", eps,
+        self._gemm("out.conv", T, ops.conv3x3_segs([(hn.ptr, hn.C, hn.C)]), "out.2.weight", eps,
                    bias=self.w["out.2.bias"], geom=ops.Geom(OH=h, OW=w, IH=h, IW=w), out_fp32=True)
         self.release(hn)
 
