@@ -1,4 +1,4 @@
-"""The rasteriser's depth mode (csrc/raster.hip gs_render_batch_depth_kernel through vmv_gs_batch_render_depth and
+"""The rasteriser's depth mode (csrc/raster.hip gs_render_batch_kernel<false, true> through vmv_gs_batch_render_depth and
 GaussianRenderer.render_depth) on the device: expected depth against the splatting oracle, median depth against the fp64 restatement
 of tests/gs_depth_ref.py (checked on the CPU in tests/test_gs_depth_cpu.py), staging past one LDS batch, the edges, batch independence,
 the store footprint, a closed form and the entrance keys.  Bounds are in ``gs_depth_ref.compare_view``."""

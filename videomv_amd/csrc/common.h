@@ -183,6 +183,13 @@ VMV_DEV float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// sum over a 256-thread block (four waves), the same value in every thread; `s_part` = 4 floats of LDS, free for reuse after a barrier
+VMV_DEV float block_sum(float v, float* s_part) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
 
 VMV_DEV bool vmv_ptr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int vmv_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }

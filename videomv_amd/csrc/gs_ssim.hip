@@ -66,13 +66,6 @@ VMV_DEV void ss_vertical(const float* __restrict__ h, const int r0, const int c,
     }
 }
 
-VMV_DEV float ss_block_sum(float v, float* s_part) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
-}
-
 // dmu / d11 / d12 == nullptr (all three together): scalars only.  The arithmetic of m does not depend on it: same bits either way.
 __global__ __launch_bounds__(256) void gs_ssim_forward_kernel(const float* __restrict__ image, const float* __restrict__ target, const SsimGeom s,
                                                               float* __restrict__ dmu, float* __restrict__ d11, float* __restrict__ d12,
@@ -148,8 +141,8 @@ __global__ __launch_bounds__(256) void gs_ssim_forward_kernel(const float* __res
             }
         }
     }
-    const float tm = ss_block_sum(sum_m, s_part[0]);
-    const float tl = ss_block_sum(sum_l1, s_part[1]);
+    const float tm = block_sum(sum_m, s_part[0]);
+    const float tl = block_sum(sum_l1, s_part[1]);
     if (threadIdx.x == 0) {
         part[2L * blockIdx.x] = tm;
         part[2L * blockIdx.x + 1] = tl;

@@ -14,8 +14,9 @@
 //   rocprim::radix_sort_pairs                    (the only library primitive: a stable 64-bit key sort)
 //   gs_ranges_kernel       first / last instance of every tile
 //   gs_render_kernel       one 256-thread block per 16x16 tile: the tile's instances are staged through LDS in batches
-//                          of 256 (xy, conic+opacity, colour), every thread blends its pixel front to back with the
-//                          1/255 alpha cut, the 0.99 clamp and the T < 1e-4 stop; block-wide early exit
+//                          of 256 (xy, conic+opacity, colour), every thread blends its pixel front to back; block-wide early exit.
+//                          The blend rule (1/255 cut, 0.99 cap, stop before T < 1e-4, the pad) is stated once, in gs_common.h, with
+//                          the projection, the staging and the pair arithmetic the backward pass (raster_bwd.hip) shares
 // Memory: everything per Gaussian is 48 B, per instance 12 B; the render pass reads each instance once per tile.
 //
 // The BATCHED pass (vmv_gs_batch_*, round 6) keeps the depth out of the big sort.  The V x N (view, Gaussian) records are first sorted by
@@ -28,67 +29,22 @@
 // binary search), so the key / value stores are coalesced (the one-thread-per-Gaussian loop wrote ~20 scattered runs per thread:
 // 0.67 ms for 32 M instances, now 0.10).  Measured and rejected on the way: the tile-id sort followed by a per-tile bitonic sort of
 // (depth, index) keys in the blend block's LDS — correct, but 2.8 ms of sorting for 24 576 tiles (profiles/r6_gs_*).
-#include "common.h"
+#include "gs_common.h"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace {
 
-constexpr int GS_TILE = 16;
-
-// One Gaussian against one view: everything gs_preprocess writes for it.  `V` / `M` = the view's cam_view / cam_view_proj (row-major,
-// row-vector convention), outputs at index `o` of the per-(view, Gaussian) arrays.  Shared by the per-view and the batched kernels, so
-// the two paths produce the same bits.
+// One Gaussian against one view: everything gs_preprocess writes for it — the projection terms of gs_common.h (GS_PROJECT_TERMS), then the 3-sigma radius,
+// the 16x16-tile rectangle and the stores.  `V` / `M` = the view's cam_view / cam_view_proj, outputs at index `o` of the per-(view,
+// Gaussian) arrays.  Shared by the per-view and the batched kernels, so the two paths produce the same bits.  Culls, in order: behind
+// the near plane, a singular 2-D covariance, a rectangle without tiles.
 struct GsOut { float* depth; float* xy; float* conic_opacity; int32_t* rect; uint32_t* tiles_touched; };
 VMV_DEV void gs_project(const float* __restrict__ g, const float* __restrict__ V, const float* __restrict__ M, const int size,
                         const float tan_half_fov, const GsOut& out, const long o) {
     out.tiles_touched[o] = 0;
-    const float mx = g[0], my = g[1], mz = g[2];
-    // row-vector convention: [m, 1] @ matrix
-    const float vx = mx * V[0] + my * V[4] + mz * V[8] + V[12];
-    const float vy = mx * V[1] + my * V[5] + mz * V[9] + V[13];
-    const float vz = mx * V[2] + my * V[6] + mz * V[10] + V[14];
-    if (!(vz > 0.2f)) return;
-    const float hx = mx * M[0] + my * M[4] + mz * M[8] + M[12];
-    const float hy = mx * M[1] + my * M[5] + mz * M[9] + M[13];
-    const float hw = mx * M[3] + my * M[7] + mz * M[11] + M[15];
-    const float iw = 1.0f / (hw + 1e-7f);
-    const float nx = hx * iw, ny = hy * iw;
-    // 3-D covariance  R diag(s^2) R^T, quaternion (r, x, y, z) used as given
-    const float sx = g[4], sy = g[5], sz = g[6];
-    const float qr = g[7], qx = g[8], qy = g[9], qz = g[10];
-    const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qr * qz), 2.f * (qx * qz + qr * qy),
-                        2.f * (qx * qy + qr * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qr * qx),
-                        2.f * (qx * qz - qr * qy), 2.f * (qy * qz + qr * qx), 1.f - 2.f * (qx * qx + qy * qy)};
-    const float s2[3] = {sx * sx, sy * sy, sz * sz};
-    float S3[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            S3[a * 3 + b] = R[a * 3 + 0] * s2[0] * R[b * 3 + 0] + R[a * 3 + 1] * s2[1] * R[b * 3 + 1] + R[a * 3 + 2] * s2[2] * R[b * 3 + 2];
-    // EWA projection: T = J W3, W3 = V[:3,:3]^T
-    const float focal = (float)size / (2.0f * tan_half_fov);
-    const float lim = 1.3f * tan_half_fov;
-    const float tx = fminf(lim, fmaxf(-lim, vx / vz)) * vz;
-    const float ty = fminf(lim, fmaxf(-lim, vy / vz)) * vz;
-    const float j00 = focal / vz, j02 = -focal * tx / (vz * vz), j11 = focal / vz, j12 = -focal * ty / (vz * vz);
-    float T0[3], T1[3];          // rows of T = J W3:  W3[r][c] = V[c*4 + r]
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        T0[c] = j00 * V[c * 4 + 0] + j02 * V[c * 4 + 2];
-        T1[c] = j11 * V[c * 4 + 1] + j12 * V[c * 4 + 2];
-    }
-    float u0[3], u1[3];          // Sigma3 T^T
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        u0[a] = S3[a * 3 + 0] * T0[0] + S3[a * 3 + 1] * T0[1] + S3[a * 3 + 2] * T0[2];
-        u1[a] = S3[a * 3 + 0] * T1[0] + S3[a * 3 + 1] * T1[1] + S3[a * 3 + 2] * T1[2];
-    }
-    const float ca = T0[0] * u0[0] + T0[1] * u0[1] + T0[2] * u0[2] + 0.3f;
-    const float cb = T0[0] * u1[0] + T0[1] * u1[1] + T0[2] * u1[2];
-    const float cc = T1[0] * u1[0] + T1[1] * u1[1] + T1[2] * u1[2] + 0.3f;
+    GS_PROJECT_TERMS(g, V, M, size, tan_half_fov, if (!(vz > 0.2f)) return);
     const float det = ca * cc - cb * cb;
     if (det == 0.0f) return;
     const float idet = 1.0f / det;
@@ -98,7 +54,7 @@ VMV_DEV void gs_project(const float* __restrict__ g, const float* __restrict__ V
     const float px = ((nx + 1.0f) * (float)size - 1.0f) * 0.5f;
     const float py = ((ny + 1.0f) * (float)size - 1.0f) * 0.5f;
     const int grid = (size + GS_TILE - 1) / GS_TILE;
-    auto clampi = [&](float v) { const int t = (int)v; return t < 0 ? 0 : (t > grid ? grid : t); };
+    auto clampi = [&](float v) { const int c = (int)v; return c < 0 ? 0 : (c > grid ? grid : c); };
     const int x0 = clampi((px - radius) / GS_TILE), y0 = clampi((py - radius) / GS_TILE);
     const int x1 = clampi((px + radius + GS_TILE - 1) / GS_TILE), y1 = clampi((py + radius + GS_TILE - 1) / GS_TILE);
     const int touched = (x1 - x0) * (y1 - y0);
@@ -217,19 +173,6 @@ __global__ __launch_bounds__(256) void gs_duplicate_batch_kernel(const VmvGsBatc
     }
 }
 
-__global__ __launch_bounds__(256) void gs_ranges_batch_kernel(const VmvGsBatchParams p) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.num_rendered) return;
-    const uint32_t* ks = reinterpret_cast<const uint32_t*>(p.keys_sorted);
-    const uint32_t t = ks[i];
-    if (i == 0) p.ranges[2 * t] = 0;
-    else {
-        const uint32_t tp = ks[i - 1];
-        if (tp != t) { p.ranges[2 * tp + 1] = (uint32_t)i; p.ranges[2 * t] = (uint32_t)i; }
-    }
-    if (i == p.num_rendered - 1) p.ranges[2 * t + 1] = (uint32_t)p.num_rendered;
-}
-
 __global__ __launch_bounds__(256) void gs_duplicate_kernel(const VmvGsParams p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.N || p.tiles_touched[i] == 0) return;
@@ -246,28 +189,30 @@ __global__ __launch_bounds__(256) void gs_duplicate_kernel(const VmvGsParams p) 
         }
 }
 
-__global__ __launch_bounds__(256) void gs_ranges_kernel(const VmvGsParams p) {
+// first / last instance of every tile from the sorted keys: uint64_t = the per-view (tile << 32 | depth bits), uint32_t = the batched
+// pass's (view, tile) id
+template <typename Key>
+__global__ __launch_bounds__(256) void gs_ranges_kernel(const Key* __restrict__ keys_sorted, uint32_t* __restrict__ ranges, const int num_rendered) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.num_rendered) return;
-    const uint32_t t = (uint32_t)(p.keys_sorted[i] >> 32);
-    if (i == 0) p.ranges[2 * t] = 0;
+    if (i >= num_rendered) return;
+    auto tile_of = [](const Key k) { if constexpr (sizeof(Key) == 8) return (uint32_t)(k >> 32); else return (uint32_t)k; };
+    const uint32_t t = tile_of(keys_sorted[i]);
+    if (i == 0) ranges[2 * t] = 0;
     else {
-        const uint32_t tp = (uint32_t)(p.keys_sorted[i - 1] >> 32);
-        if (tp != t) { p.ranges[2 * tp + 1] = (uint32_t)i; p.ranges[2 * t] = (uint32_t)i; }
+        const uint32_t tp = tile_of(keys_sorted[i - 1]);
+        if (tp != t) { ranges[2 * tp + 1] = (uint32_t)i; ranges[2 * t] = (uint32_t)i; }
     }
-    if (i == p.num_rendered - 1) p.ranges[2 * t + 1] = (uint32_t)p.num_rendered;
+    if (i == num_rendered - 1) ranges[2 * t + 1] = (uint32_t)num_rendered;
 }
 
 // One 16 x 16 tile of one view: blend the tile's sorted instances [lo, hi) front to back.  Arrays are the view's own (already offset).
-// `order(j)` = Gaussian index of the tile's j-th instance in blend order, j in [lo, hi).
+// `order[j]` = Gaussian index of the tile's j-th instance in blend order, j in [lo, hi).
 // Round 6: the inner loop is branch-free per lane and wave-uniform in its control flow.  The divergent form (three nested `continue` /
 // `break` tests) spent as many scalar mask instructions as vector ones — 35 + 35 per Gaussian and wave in the ISA — on a kernel that is
-// VALU-bound (8 G pixel x Gaussian evaluations per 24 views; it was priced against HBM before, wrongly).  Now the exponent is taken in
-// base 2 with the conic pre-scaled by -0.5 log2(e) when the Gaussian is staged (one v_exp_f32 instead of expf's range reduction), a
-// WAVE skips a PAIR of Gaussians none of its 64 pixels can see (conservative pre-test on p2 + log2(opacity), before the exponential;
-// the pair's exponents are packed fp32 operations), the
-// per-lane tests are selects, and the loop leaves when every lane of the wave is done.  Same rule as before per pixel: skip power > 0,
-// alpha = min(0.99, opacity e^power), skip alpha < 1/255, stop BEFORE the Gaussian that would take T below 1e-4.
+// VALU-bound (8 G pixel x Gaussian evaluations per 24 views; it was priced against HBM before, wrongly).  Now a WAVE skips a PAIR of
+// staged Gaussians none of its 64 pixels can see (the pre-test of gs_pair_falloff, before the exponential), the per-lane tests are
+// selects, and the loop leaves when every lane of the wave is done.  The rule per pixel (skip, alpha, stop) and the staging are those of
+// gs_common.h, which says why each is what it is.
 // STATE (the fitter's forward, vmv_gs_batch_render_state): also write every pixel's final T and the count of the tile's instances up to and
 // including the last one it blended — what the backward pass (raster_bwd.hip) walks.  STATE = false is the production blend, unchanged.
 // DEPTH (vmv_gs_batch_render_depth): every staged Gaussian also carries its view depth z (`depth`, the preprocess array the sort keys
@@ -277,16 +222,15 @@ __global__ __launch_bounds__(256) void gs_ranges_kernel(const VmvGsParams p) {
 // one FMA, one compare and selects per (pixel, Gaussian); the control flow stays wave-uniform.  A Gaussian that triggers the T < 1e-4
 // stop is not applied and T was below 0.01 before it, so the crossing is always recorded before a wave leaves on saturation.
 // DEPTH = false instantiates none of it: no LDS array, no registers.
-template <bool STATE = false, bool DEPTH = false, typename Order>
+template <bool STATE = false, bool DEPTH = false>
 VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const uint32_t lo, const uint32_t hi,
-                           const Order order, const float* __restrict__ xy, const float* __restrict__ conic_opacity,
+                           const uint32_t* __restrict__ order, const float* __restrict__ xy, const float* __restrict__ conic_opacity,
                            const float* __restrict__ gaussians, float* __restrict__ out_color, float* __restrict__ out_alpha,
                            float* __restrict__ out_T = nullptr, int32_t* __restrict__ out_count = nullptr,
                            const float* __restrict__ depth = nullptr, float* __restrict__ out_depth = nullptr,
                            float* __restrict__ out_median = nullptr) {
-    // staged Gaussians, one array per field (+ 2 pad entries): the loop takes them TWO at a time, a field pair is one ds_read_b64 and
-    // the falloff exponents of the pair are packed fp32 operations (v_pk_*: 8 for two Gaussians where the one-at-a-time form issued 16)
     __shared__ __attribute__((aligned(16))) float s_x[258], s_y[258], s_A[258], s_B[258], s_C[258], s_l[258], s_o[258], s_r[258], s_g[258], s_b[258];
+    const GsTileRef s{s_x, s_y, s_A, s_B, s_C, s_l, s_o, s_r, s_g, s_b};
     __shared__ int s_done;
     float* s_z = nullptr;
     if constexpr (DEPTH) {
@@ -300,41 +244,30 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
     int32_t last = 0;                          // (STATE only) instances [lo, lo + last) reach this pixel's last blended one
     float D = 0.f, med = 0.f;                  // (DEPTH only)
     bool done = !inside;
-    constexpr float LOG2E = 1.4426950408889634f;
-    constexpr float CULL = -7.9943534f - 0.02f;      // log2(1 / 255) with a margin: the exact alpha test follows for what passes
     for (uint32_t base = lo; base < hi; base += 256) {
         if (threadIdx.x == 0) s_done = 0;
         __syncthreads();
         const uint32_t j = base + threadIdx.x;
         if (j < hi) {
-            const uint32_t gi = order(j);
-            const float* co = conic_opacity + 4L * gi;
-            const float* g = gaussians + 14L * gi + 11;
-            const float o = co[3];
-            s_x[threadIdx.x] = xy[2 * gi]; s_y[threadIdx.x] = xy[2 * gi + 1];
-            s_A[threadIdx.x] = -0.5f * LOG2E * co[0]; s_B[threadIdx.x] = -LOG2E * co[1]; s_C[threadIdx.x] = -0.5f * LOG2E * co[2];
-            s_l[threadIdx.x] = o > 0.f ? __builtin_amdgcn_logf(o) : -1e30f;      // v_log_f32: log2
-            s_o[threadIdx.x] = o;
-            s_r[threadIdx.x] = g[0]; s_g[threadIdx.x] = g[1]; s_b[threadIdx.x] = g[2];
+            const uint32_t gi = order[j];
+            gs_stage(s, threadIdx.x, gi, xy, conic_opacity, gaussians);
             if constexpr (DEPTH) s_z[threadIdx.x] = depth[gi];
-        } else {                               // pad: a Gaussian nobody sees (the pair of an odd tail)
-            s_x[threadIdx.x] = 0.f; s_y[threadIdx.x] = 0.f; s_A[threadIdx.x] = 0.f; s_B[threadIdx.x] = 0.f; s_C[threadIdx.x] = 0.f;
-            s_l[threadIdx.x] = -1e30f; s_o[threadIdx.x] = 0.f;
-            s_r[threadIdx.x] = 0.f; s_g[threadIdx.x] = 0.f; s_b[threadIdx.x] = 0.f;      // (weight 0 x stale LDS could be 0 x NaN)
+        } else {                               // the pair of an odd tail
+            gs_stage_pad(s, threadIdx.x);
             if constexpr (DEPTH) s_z[threadIdx.x] = 0.f;
         }
         __syncthreads();
         const int n = (int)min(256u, hi - base);
         // one Gaussian against this lane's pixel (p2 = log2 of its falloff there, already known to pass the pre-test in some lane)
         auto blend_one = [&](const int k, const float p2, const bool maybe) {
-            const float alpha = fminf(0.99f, s_o[k] * __builtin_amdgcn_exp2f(p2));
-            const bool valid = maybe && !done && alpha >= 1.0f / 255.0f;
+            const float alpha = gs_alpha(s, k, gs_falloff(p2));
+            const bool valid = maybe && !done && alpha >= GS_ALPHA_MIN;
             const float tT = T * (1.0f - alpha);
             const bool stop = valid && tT < 1e-4f;
             done = done || stop;
             const bool apply = valid && !stop;
             const float w = apply ? alpha * T : 0.0f;
-            C0 += s_r[k] * w; C1 += s_g[k] * w; C2 += s_b[k] * w; Wt += w;
+            C0 += s.r[k] * w; C1 += s.g[k] * w; C2 += s.b[k] * w; Wt += w;
             T = apply ? tT : T;
             if constexpr (STATE) last = apply ? (int32_t)(base - lo) + k + 1 : last;
             if constexpr (DEPTH) {
@@ -343,16 +276,11 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
                 med = (apply && tT < 0.5f && med == 0.0f) ? z : med;
             }
         };
-        const f32x2_t fx2 = {fx, fx}, fy2 = {fy, fy};
         for (int k = 0; k < n; k += 2) {       // (entry n of an odd n is a pad or, in a full batch, never read: n = 256 is even)
-            const f32x2_t dx = *reinterpret_cast<const f32x2_t*>(s_x + k) - fx2, dy = *reinterpret_cast<const f32x2_t*>(s_y + k) - fy2;
-            const f32x2_t p2 = *reinterpret_cast<const f32x2_t*>(s_A + k) * dx * dx + *reinterpret_cast<const f32x2_t*>(s_C + k) * dy * dy +
-                               *reinterpret_cast<const f32x2_t*>(s_B + k) * dx * dy;
-            const f32x2_t pre = p2 + *reinterpret_cast<const f32x2_t*>(s_l + k);
-            const bool m0 = p2.x <= 0.0f && pre.x >= CULL, m1 = p2.y <= 0.0f && pre.y >= CULL;
-            if (__builtin_amdgcn_ballot_w64(!done && (m0 || m1)) == 0) continue;      // nobody in the wave sees either
-            blend_one(k, p2.x, m0);
-            blend_one(k + 1, p2.y, m1);
+            const GsPair f = gs_pair_falloff(s, k, fx, fy);
+            if (__builtin_amdgcn_ballot_w64(!done && (f.m0 || f.m1)) == 0) continue;   // nobody in the wave sees either
+            blend_one(k, f.p2.x, f.m0);
+            blend_one(k + 1, f.p2.y, f.m1);
             if (__builtin_amdgcn_ballot_w64(!done) == 0) break;                        // the whole wave is saturated
         }
         if (!done) s_done = 1;                 // somebody still needs more Gaussians
@@ -378,49 +306,21 @@ VMV_DEV void gs_blend_tile(const int size, const float* __restrict__ bg, const u
 __global__ __launch_bounds__(256) void gs_render_kernel(const VmvGsParams p) {
     const int grid = (p.size + GS_TILE - 1) / GS_TILE;
     const int tile = blockIdx.y * grid + blockIdx.x;
-    const uint32_t* vs = p.vals_sorted;
-    gs_blend_tile(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy, p.conic_opacity,
-                  p.gaussians, p.out_color, p.out_alpha);
+    gs_blend_tile(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], p.vals_sorted, p.xy, p.conic_opacity, p.gaussians, p.out_color,
+                  p.out_alpha);
 }
 
-__global__ __launch_bounds__(256) void gs_render_batch_kernel(const VmvGsBatchParams p) {
-    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
-    const int vv = blockIdx.z;
-    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
-    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
-    // (a view without instances has ranges 0 / 0 from the memset: the tile writes the background)
-    const uint32_t* vs = p.vals_sorted;
-    gs_blend_tile(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy + 2 * vo,
-                  p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
-                  p.out_alpha ? p.out_alpha + hw * vv : nullptr);
-}
-
-// the fitter's forward: the same blend with the per-pixel state of VmvGsBackwardParams
-__global__ __launch_bounds__(256) void gs_render_batch_state_kernel(const VmvGsBatchParams p, float* __restrict__ final_T,
-                                                                    int32_t* __restrict__ n_contrib) {
-    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
-    const int vv = blockIdx.z;
-    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
-    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
-    const uint32_t* vs = p.vals_sorted;
-    gs_blend_tile<true>(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; }, p.xy + 2 * vo,
-                        p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
-                        p.out_alpha ? p.out_alpha + hw * vv : nullptr, final_T + hw * vv, n_contrib + hw * vv);
-}
-
-// the batched blend with the depth mode on: expected and median depth next to the same image and alpha
-__global__ __launch_bounds__(256) void gs_render_batch_depth_kernel(const VmvGsBatchParams p, float* __restrict__ out_depth,
-                                                                    float* __restrict__ out_median) {
-    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
-    const int vv = blockIdx.z;
-    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
-    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
-    // (a tile or view without instances has ranges 0 / 0: the background, D = 0, median = 0)
-    const uint32_t* vs = p.vals_sorted;
-    gs_blend_tile<false, true>(p.size, p.bg, p.ranges[2 * tile], p.ranges[2 * tile + 1], [vs](const uint32_t j) { return vs[j]; },
-                               p.xy + 2 * vo, p.conic_opacity + 4 * vo, p.gaussians + (long)(vv / p.V) * p.N * 14, p.out_color + 3 * hw * vv,
-                               p.out_alpha ? p.out_alpha + hw * vv : nullptr, nullptr, nullptr, p.depth + vo, out_depth + hw * vv,
-                               out_median ? out_median + hw * vv : nullptr);
+// The batched blend: tile (x, y) of view blockIdx.z.  <false, false> is the production blend (vmv_gs_batch_render), STATE the fitter's
+// forward with the per-pixel state of VmvGsBackwardParams (final_T, n_contrib), DEPTH the depth mode (out_depth, optional out_median)
+// next to the same image and alpha; the pointers of a mode that is off are not read.  A tile or view without instances blends nothing:
+// the background, alpha 0, T = 1, count 0, D = 0, median 0.
+template <bool STATE, bool DEPTH>
+__global__ __launch_bounds__(256) void gs_render_batch_kernel(const VmvGsBatchParams p, float* __restrict__ final_T, int32_t* __restrict__ n_contrib,
+                                                              float* __restrict__ out_depth, float* __restrict__ out_median) {
+    const GsTileView t = gs_tile_view(p);
+    gs_blend_tile<STATE, DEPTH>(p.size, p.bg, t.lo, t.hi, p.vals_sorted, t.xy, t.conic_opacity, t.gaussians, t.out_color, t.out_alpha,
+                                STATE ? final_T + t.pix : nullptr, STATE ? n_contrib + t.pix : nullptr, DEPTH ? p.depth + t.vo : nullptr,
+                                DEPTH ? out_depth + t.pix : nullptr, DEPTH && out_median ? out_median + t.pix : nullptr);
 }
 
 int gs_check(const VmvGsParams& p) {
@@ -477,7 +377,8 @@ extern "C" int vmv_gs_render(const VmvGsParams* pp, void* stream) {
         e = rocprim::radix_sort_pairs(p.sort_temp, bytes, p.keys, p.keys_sorted, p.vals, p.vals_sorted, (size_t)p.num_rendered,
                                       0u, (unsigned)(32 + tile_bits), st);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(gs_ranges_kernel, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(gs_ranges_kernel<uint64_t>, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st, (const uint64_t*)p.keys_sorted,
+                           p.ranges, p.num_rendered);
     }
     hipLaunchKernelGGL(gs_render_kernel, dim3(grid, grid), dim3(256), 0, st, p);
     return vmv_launch_status();
@@ -488,10 +389,9 @@ namespace {
 int gs_batch_check(const VmvGsBatchParams& p) {
     if (!p.gaussians || !p.views || !p.view_projs || !p.depth || !p.xy || !p.conic_opacity || !p.rect || !p.tiles_touched || !p.offsets)
         return VMV_ENULL;
-    if (p.B <= 0 || p.V <= 0 || p.N <= 0 || p.size <= 0 || !(p.tan_half_fov > 0.f)) return VMV_EINVAL;
-    const long grid = (p.size + GS_TILE - 1) / GS_TILE;
-    if ((long)p.B * p.V > 65535 || (long)p.B * p.V * p.N >= (1L << 31) || (long)p.B * p.V * grid * grid >= (1L << 31)) return VMV_ERANGE;
-    return VMV_OK;
+    const int rc = gs_batch_limits(p);
+    if (rc != VMV_OK) return rc;
+    return (long)p.B * p.V * p.N >= (1L << 31) ? VMV_ERANGE : VMV_OK;      // record indices o = vv * N + i are 32-bit (perm[])
 }
 }  // namespace
 
@@ -569,11 +469,13 @@ int gs_batch_render(const VmvGsBatchParams* pp, float* final_T, int32_t* n_contr
         e = rocprim::radix_sort_pairs(p.sort_temp, bytes, reinterpret_cast<uint32_t*>(p.keys), reinterpret_cast<uint32_t*>(p.keys_sorted),
                                       p.vals, p.vals_sorted, (size_t)p.num_rendered, 0u, (unsigned)(vmv_gs_batch_key_bits(VV, p.size) - 32), st);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(gs_ranges_batch_kernel, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(gs_ranges_kernel<uint32_t>, dim3((p.num_rendered + 255) / 256), dim3(256), 0, st,
+                           reinterpret_cast<const uint32_t*>(p.keys_sorted), p.ranges, p.num_rendered);
     }
-    if (out_depth) hipLaunchKernelGGL(gs_render_batch_depth_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, out_depth, out_median);
-    else if (final_T) hipLaunchKernelGGL(gs_render_batch_state_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p, final_T, n_contrib);
-    else hipLaunchKernelGGL(gs_render_batch_kernel, dim3(grid, grid, VV), dim3(256), 0, st, p);
+    const dim3 tiles(grid, grid, VV);
+    if (out_depth) hipLaunchKernelGGL((gs_render_batch_kernel<false, true>), tiles, dim3(256), 0, st, p, final_T, n_contrib, out_depth, out_median);
+    else if (final_T) hipLaunchKernelGGL((gs_render_batch_kernel<true, false>), tiles, dim3(256), 0, st, p, final_T, n_contrib, out_depth, out_median);
+    else hipLaunchKernelGGL((gs_render_batch_kernel<false, false>), tiles, dim3(256), 0, st, p, final_T, n_contrib, out_depth, out_median);
     return vmv_launch_status();
 }
 }  // namespace

@@ -2,55 +2,44 @@
 // fit Gaussians to a view set (videomv_amd/gs_fit.py; contract in include/vmv.h, "Fitting Gaussians to a view set").  All fp32.
 //
 //   gs_blend_backward_kernel    one 256-thread block per (view, 16x16 tile): walks the tile's instances BACK TO FRONT from the largest
-//                               n_contrib of its pixels, in the forward's chunks of 256 and with the forward's pair arithmetic (base-2
-//                               exponent, pre-scaled conic), recovers T before each Gaussian from the final T, and sums each instance's
+//                               n_contrib of its pixels, in the forward's chunks of 256 and through the forward's own staging, pair
+//                               arithmetic and alpha (gs_common.h, which states the blend rule and why the 0.99 cap and the stop before
+//                               T < 1e-4 make this walk safe), recovers T before each Gaussian from the final T, and sums each instance's
 //                               9 screen-space gradients over the tile's pixels on chip — a wave reduction, then one LDS add per wave —
 //                               before ONE atomicAdd(float*) per value and instance into grad2d (why atomics)
-//   gs_preprocess_backward_kernel  one thread per (view, Gaussian): grad2d -> the 14-float activated layout, plain stores
+//   gs_preprocess_backward_kernel  one thread per (view, Gaussian): the forward's projection terms (GS_PROJECT_TERMS), then the chain
+//                               rule from grad2d to the 14-float activated layout, plain stores
 //   gs_view_sum_kernel          grad[b][i] = sum over v of grad_view[b][v][i], in view order (deterministic)
 //   gs_loss_partial_kernel / gs_loss_final_kernel   MSE + dL/dimage, per-block partials summed by one block in a fixed order
 //   gs_adam_kernel              one thread per Gaussian: activation Jacobians, bias-corrected Adam, activated output
-#include "common.h"
+#include "gs_common.h"
 
 namespace {
 
-constexpr int GS_TILE = 16;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float CULL = -7.9943534f - 0.02f;      // raster.hip gs_blend_tile: log2(1 / 255) with a margin
-constexpr float SH_C0 = 0.28209479177387814f;
-
-VMV_DEV float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
+// The chunk is staged like the forward's (gs_stage), but padded differently: the forward pads j >= hi, this kernel pads every slot
+// >= n, where n comes from the tile's largest n_contrib — instances behind it exist in vals_sorted but no pixel of the tile blended them.
+// Each pixel takes the forward's decision again (gs_pair_falloff, gs_alpha, the 1/255 cut) for the instances below ITS n_contrib; the
+// stop needs no replay: n_contrib ends before the Gaussian that triggered it.
 __global__ __launch_bounds__(256) void gs_blend_backward_kernel(const VmvGsBackwardParams q) {
     const VmvGsBatchParams& p = q.pass;
-    __shared__ __attribute__((aligned(16))) float s_x[258], s_y[258], s_A[258], s_B[258], s_C[258], s_l[258], s_o[258];
-    __shared__ float s_r[256], s_g[256], s_b[256], s_ca[256], s_cb[256], s_cc[256];
+    __shared__ __attribute__((aligned(16))) GsTile s;
+    __shared__ float s_ca[256], s_cb[256], s_cc[256];      // the raw conic (the gradient of the centre)
     __shared__ uint32_t s_gi[256];
     __shared__ float s_grad[9][256];
     __shared__ int s_max;
-    const int grid = (p.size + GS_TILE - 1) / GS_TILE;
-    const int vv = blockIdx.z;
-    const long tile = (long)vv * grid * grid + blockIdx.y * grid + blockIdx.x;
-    const long hw = (long)p.size * p.size, vo = (long)vv * p.N;
-    const uint32_t lo = p.ranges[2 * tile];
-    const float* xy = p.xy + 2 * vo;
-    const float* co = p.conic_opacity + 4 * vo;
-    const float* gs = p.gaussians + (long)(vv / p.V) * p.N * 14;
+    const GsTileView t = gs_tile_view(p);
     const int px = blockIdx.x * GS_TILE + (threadIdx.x & 15), py = blockIdx.y * GS_TILE + (threadIdx.x >> 4);
     const bool inside = px < p.size && py < p.size;
     const float fx = (float)px, fy = (float)py;
+    const long hw = t.hw;
     int cnt = 0;
     float T = 1.0f, d0 = 0.f, d1 = 0.f, d2 = 0.f;
     if (inside) {
         const long o = (long)py * p.size + px;
-        cnt = q.n_contrib[hw * vv + o];
-        T = q.final_T[hw * vv + o];
-        const float* img = p.out_color + 3 * hw * vv + o;
-        const float* dl = q.dL_dimage + 3 * hw * vv + o;
+        cnt = q.n_contrib[t.pix + o];
+        T = q.final_T[t.pix + o];
+        const float* img = t.out_color + o;
+        const float* dl = q.dL_dimage + 3 * t.pix + o;
         // clamp(0, 1) of the output: no gradient where it clamped
         d0 = (img[0] > 0.f && img[0] < 1.f) ? dl[0] : 0.f;
         d1 = (img[hw] > 0.f && img[hw] < 1.f) ? dl[hw] : 0.f;
@@ -68,33 +57,24 @@ __global__ __launch_bounds__(256) void gs_blend_backward_kernel(const VmvGsBackw
     float a0 = 0.f, a1 = 0.f, a2 = 0.f;          // colour of what lies behind the current Gaussian, per unit transmittance
     const int lane = threadIdx.x & 63;
     for (int c = (nmax - 1) >> 8; c >= 0 && nmax > 0; --c) {
-        const uint32_t base = lo + 256u * (uint32_t)c;
+        const uint32_t base = t.lo + 256u * (uint32_t)c;
         const int n = min(256, nmax - 256 * c);
         if ((int)threadIdx.x < n) {
             const uint32_t gi = p.vals_sorted[base + threadIdx.x];
-            const float* cg = co + 4L * gi;
-            const float* g = gs + 14L * gi + 11;
-            const float o = cg[3];
-            s_x[threadIdx.x] = xy[2 * gi]; s_y[threadIdx.x] = xy[2 * gi + 1];
-            s_A[threadIdx.x] = -0.5f * LOG2E * cg[0]; s_B[threadIdx.x] = -LOG2E * cg[1]; s_C[threadIdx.x] = -0.5f * LOG2E * cg[2];
-            s_l[threadIdx.x] = o > 0.f ? __builtin_amdgcn_logf(o) : -1e30f;
-            s_o[threadIdx.x] = o;
-            s_r[threadIdx.x] = g[0]; s_g[threadIdx.x] = g[1]; s_b[threadIdx.x] = g[2];
+            const float* cg = t.conic_opacity + 4L * gi;
+            gs_stage(s, threadIdx.x, gi, t.xy, t.conic_opacity, t.gaussians);
             s_ca[threadIdx.x] = cg[0]; s_cb[threadIdx.x] = cg[1]; s_cc[threadIdx.x] = cg[2];
             s_gi[threadIdx.x] = gi;
         } else {
-            s_x[threadIdx.x] = 0.f; s_y[threadIdx.x] = 0.f; s_A[threadIdx.x] = 0.f; s_B[threadIdx.x] = 0.f; s_C[threadIdx.x] = 0.f;
-            s_l[threadIdx.x] = -1e30f; s_o[threadIdx.x] = 0.f;
-            s_r[threadIdx.x] = 0.f; s_g[threadIdx.x] = 0.f; s_b[threadIdx.x] = 0.f;
+            gs_stage_pad(s, threadIdx.x);
             s_ca[threadIdx.x] = 0.f; s_cb[threadIdx.x] = 0.f; s_cc[threadIdx.x] = 0.f; s_gi[threadIdx.x] = 0u;
         }
         __syncthreads();
         auto back_one = [&](const int k, const float p2, const bool maybe) {
             const int jr = 256 * c + k;
-            const float G = __builtin_amdgcn_exp2f(p2);
-            const float ag = s_o[k] * G;
-            const float alpha = fminf(0.99f, ag);
-            const bool hit = maybe && jr < cnt && alpha >= 1.0f / 255.0f;
+            const float G = gs_falloff(p2);
+            const float alpha = gs_alpha(s, k, G);
+            const bool hit = maybe && jr < cnt && alpha >= GS_ALPHA_MIN;
             if (__builtin_amdgcn_ballot_w64(hit) == 0) return;
             float g[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             if (hit) {
@@ -102,11 +82,11 @@ __global__ __launch_bounds__(256) void gs_blend_backward_kernel(const VmvGsBackw
                 T = T / om;                      // transmittance in front of this Gaussian
                 const float w = alpha * T;
                 g[6] = w * d0; g[7] = w * d1; g[8] = w * d2;
-                const float dla = T * ((s_r[k] - a0) * d0 + (s_g[k] - a1) * d1 + (s_b[k] - a2) * d2) - Tf / om * bgdot;
-                a0 = alpha * s_r[k] + om * a0; a1 = alpha * s_g[k] + om * a1; a2 = alpha * s_b[k] + om * a2;
-                if (ag < 0.99f) {                // alpha = o e^power below the cap
+                const float dla = T * ((s.r[k] - a0) * d0 + (s.g[k] - a1) * d1 + (s.b[k] - a2) * d2) - Tf / om * bgdot;
+                a0 = alpha * s.r[k] + om * a0; a1 = alpha * s.g[k] + om * a1; a2 = alpha * s.b[k] + om * a2;
+                if (alpha < 0.99f) {             // alpha = o e^power below the cap
                     const float dlp = dla * alpha;
-                    const float dx = s_x[k] - fx, dy = s_y[k] - fy;
+                    const float dx = s.x[k] - fx, dy = s.y[k] - fy;
                     g[0] = -dlp * (s_ca[k] * dx + s_cb[k] * dy);
                     g[1] = -dlp * (s_cc[k] * dy + s_cb[k] * dx);
                     g[2] = -0.5f * dlp * dx * dx;
@@ -117,26 +97,21 @@ __global__ __launch_bounds__(256) void gs_blend_backward_kernel(const VmvGsBackw
             }
 #pragma unroll
             for (int f = 0; f < 9; ++f) {
-                const float s = wave_sum(g[f]);
-                if (lane == 0 && s != 0.f) atomicAdd(&s_grad[f][k], s);
+                const float sum = wave_sum(g[f]);
+                if (lane == 0 && sum != 0.f) atomicAdd(&s_grad[f][k], sum);
             }
         };
-        const f32x2_t fx2 = {fx, fx}, fy2 = {fy, fy};
         for (int k = (n - 1) & ~1; k >= 0; k -= 2) {      // the forward's pairs (k, k + 1), k even, taken in reverse
-            const f32x2_t dx = *reinterpret_cast<const f32x2_t*>(s_x + k) - fx2, dy = *reinterpret_cast<const f32x2_t*>(s_y + k) - fy2;
-            const f32x2_t p2 = *reinterpret_cast<const f32x2_t*>(s_A + k) * dx * dx + *reinterpret_cast<const f32x2_t*>(s_C + k) * dy * dy +
-                               *reinterpret_cast<const f32x2_t*>(s_B + k) * dx * dy;
-            const f32x2_t pre = p2 + *reinterpret_cast<const f32x2_t*>(s_l + k);
-            const bool m0 = p2.x <= 0.0f && pre.x >= CULL, m1 = p2.y <= 0.0f && pre.y >= CULL;
-            if (__builtin_amdgcn_ballot_w64((m0 && k < cnt - 256 * c) || (m1 && k + 1 < cnt - 256 * c)) == 0) continue;
-            back_one(k + 1, p2.y, m1);
-            back_one(k, p2.x, m0);
+            const GsPair f = gs_pair_falloff(s, k, fx, fy);
+            if (__builtin_amdgcn_ballot_w64((f.m0 && k < cnt - 256 * c) || (f.m1 && k + 1 < cnt - 256 * c)) == 0) continue;
+            back_one(k + 1, f.p2.y, f.m1);
+            back_one(k, f.p2.x, f.m0);
         }
         __syncthreads();
         for (int idx = threadIdx.x; idx < 9 * n; idx += 256) {
             const int slot = idx / 9, f = idx - 9 * slot;
             const float v = s_grad[f][slot];
-            if (v != 0.f) atomicAdd(q.grad2d + (vo + s_gi[slot]) * 9 + f, v);
+            if (v != 0.f) atomicAdd(q.grad2d + (t.vo + s_gi[slot]) * 9 + f, v);
             s_grad[f][slot] = 0.f;
         }
         __syncthreads();
@@ -164,49 +139,8 @@ __global__ __launch_bounds__(256) void gs_preprocess_backward_kernel(const VmvGs
     const float* M = s_m + 16;
     const float* g = p.gaussians + ((long)(vv / p.V) * p.N + i) * 14;
     const float* g2 = q.grad2d + 9 * o;
-    const float mx = g[0], my = g[1], mz = g[2];
-    const float vx = mx * V[0] + my * V[4] + mz * V[8] + V[12];
-    const float vy = mx * V[1] + my * V[5] + mz * V[9] + V[13];
-    const float vz = mx * V[2] + my * V[6] + mz * V[10] + V[14];
-    const float hx = mx * M[0] + my * M[4] + mz * M[8] + M[12];
-    const float hy = mx * M[1] + my * M[5] + mz * M[9] + M[13];
-    const float hw = mx * M[3] + my * M[7] + mz * M[11] + M[15];
-    const float iw = 1.0f / (hw + 1e-7f);
-    const float nx = hx * iw, ny = hy * iw;
-    const float sx = g[4], sy = g[5], sz = g[6];
-    const float qr = g[7], qx = g[8], qy = g[9], qz = g[10];
-    const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qr * qz), 2.f * (qx * qz + qr * qy),
-                        2.f * (qx * qy + qr * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qr * qx),
-                        2.f * (qx * qz - qr * qy), 2.f * (qy * qz + qr * qx), 1.f - 2.f * (qx * qx + qy * qy)};
-    const float s2[3] = {sx * sx, sy * sy, sz * sz};
-    float S3[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            S3[a * 3 + b] = R[a * 3 + 0] * s2[0] * R[b * 3 + 0] + R[a * 3 + 1] * s2[1] * R[b * 3 + 1] + R[a * 3 + 2] * s2[2] * R[b * 3 + 2];
-    const float focal = (float)p.size / (2.0f * p.tan_half_fov);
-    const float lim = 1.3f * p.tan_half_fov;
-    const float rx = vx / vz, ry = vy / vz;
-    const float tx = fminf(lim, fmaxf(-lim, rx)) * vz;
-    const float ty = fminf(lim, fmaxf(-lim, ry)) * vz;
+    GS_PROJECT_TERMS(g, V, M, p.size, p.tan_half_fov, (void)0);      // (tiles_touched != 0: it passed the forward's near cull)
     const float iz = 1.0f / vz;
-    const float j00 = focal * iz, j02 = -focal * tx * iz * iz, j12 = -focal * ty * iz * iz;
-    float T0[3], T1[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        T0[c] = j00 * V[c * 4 + 0] + j02 * V[c * 4 + 2];
-        T1[c] = j00 * V[c * 4 + 1] + j12 * V[c * 4 + 2];
-    }
-    float u0[3], u1[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        u0[a] = S3[a * 3 + 0] * T0[0] + S3[a * 3 + 1] * T0[1] + S3[a * 3 + 2] * T0[2];
-        u1[a] = S3[a * 3 + 0] * T1[0] + S3[a * 3 + 1] * T1[1] + S3[a * 3 + 2] * T1[2];
-    }
-    const float ca = T0[0] * u0[0] + T0[1] * u0[1] + T0[2] * u0[2] + 0.3f;
-    const float cb = T0[0] * u1[0] + T0[1] * u1[1] + T0[2] * u1[2];
-    const float cc = T1[0] * u1[0] + T1[1] * u1[1] + T1[2] * u1[2] + 0.3f;
     const float idet = 1.0f / (ca * cc - cb * cb);
     const float id2 = idet * idet;
     // conic (A, B, C) = (cc, -cb, ca) / det
@@ -286,13 +220,6 @@ __global__ __launch_bounds__(256) void gs_view_sum_kernel(const float* __restric
 
 constexpr int LOSS_BLOCKS = 1024;
 
-VMV_DEV float block_sum(float v, float* s_part) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
-}
-
 __global__ __launch_bounds__(256) void gs_loss_partial_kernel(const float* __restrict__ image, const float* __restrict__ target, const long n,
                                                               float* __restrict__ dL, float* __restrict__ part) {
     __shared__ float s_part[4];
@@ -369,9 +296,10 @@ int gs_bwd_check(const VmvGsBackwardParams& q) {
     if (!p.gaussians || !p.views || !p.view_projs || !p.xy || !p.conic_opacity || !p.tiles_touched || !p.ranges || !p.out_color ||
         !q.final_T || !q.n_contrib || !q.dL_dimage || !q.grad2d || !q.grad_view || !q.grad)
         return VMV_ENULL;
-    if (p.B <= 0 || p.V <= 0 || p.N <= 0 || p.size <= 0 || !(p.tan_half_fov > 0.f) || p.num_rendered < 0) return VMV_EINVAL;
-    const long grid = (p.size + GS_TILE - 1) / GS_TILE;
-    if ((long)p.B * p.V > 65535 || (long)p.B * p.V * p.N * 14 >= (1L << 31) || (long)p.B * p.V * grid * grid >= (1L << 31)) return VMV_ERANGE;
+    if (p.num_rendered < 0) return VMV_EINVAL;
+    const int rc = gs_batch_limits(p);
+    if (rc != VMV_OK) return rc;
+    if ((long)p.B * p.V * p.N * 14 >= (1L << 31)) return VMV_ERANGE;      // grad_view elements
     if (p.num_rendered > 0 && !p.vals_sorted) return VMV_ENULL;
     return VMV_OK;
 }

@@ -108,16 +108,32 @@ class GaussianRenderer:
             self._buf[key] = b
         return b
 
-    def _grow(self, b, N, n, device):
-        if n <= b["cap"]:
-            return
-        cap = max(int(n * 1.25), 1 << 16)
-        sb, so = C.c_size_t(0), C.c_size_t(0)
-        L.check(L.load().vmv_gs_workspace_bytes(N, cap, C.byref(sb), C.byref(so)), "gs_workspace_bytes")
-        i64 = lambda: torch.zeros(cap, dtype=torch.int64, device=device)
-        i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=device)
-        b.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
-                 sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=device))
+    @staticmethod
+    def _attach_instances(p, buf, n, device, workspace_bytes):
+        """The binning buffers of ``n`` instances for the pass ``p`` (GsParams or GsBatchParams), shared by the per-view and the batched
+        path: grows the key / value / sort buffers of ``buf`` with 1.25 head-room (``workspace_bytes(cap, scan_ref, sort_ref)`` = the
+        path's own workspace-size call) and attaches them, the count and the ranges to ``p``."""
+        if n > buf["cap"]:
+            cap = max(int(n * 1.25), 1 << 16)
+            sb, so = C.c_size_t(0), C.c_size_t(0)
+            L.check(workspace_bytes(cap, C.byref(sb), C.byref(so)), "gs_workspace_bytes")
+            i64 = lambda: torch.zeros(cap, dtype=torch.int64, device=device)
+            i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=device)
+            buf.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
+                       sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=device))
+        p.num_rendered = n
+        if n > 0:
+            p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(), buf["vals"].data_ptr(),
+                                                            buf["vals_s"].data_ptr())
+            p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
+        p.ranges = buf["ranges"].data_ptr()
+
+    @staticmethod
+    def _attach_preprocess(p, buf):
+        """the per-Gaussian arrays and the scan workspace of ``buf`` for the pass ``p`` (GsParams or GsBatchParams)"""
+        p.depth, p.xy, p.conic_opacity, p.rect = buf["depth"].data_ptr(), buf["xy"].data_ptr(), buf["co"].data_ptr(), buf["rect"].data_ptr()
+        p.tiles_touched, p.offsets = buf["touched"].data_ptr(), buf["offsets"].data_ptr()
+        p.scan_temp, p.scan_temp_bytes = buf["scan"].data_ptr(), buf["scan"].numel()
 
     def _batch_buffers(self, B, V, N, device):
         key = ("batch", B, V, N, str(device))
@@ -137,25 +153,18 @@ class GaussianRenderer:
             self._buf[key] = b
         return b
 
-    def _render_batch(self, gaussians, cam_view, cam_view_proj, bg, images, alphas, depths=None, medians=None):
-        """All B * V views in one pass (vmv.h VmvGsBatchParams); with ``depths`` / ``medians`` the blend is the depth mode's
-        (VmvGsDepthParams: the same pass, the same image and alpha bits)."""
+    def _batch_setup(self, p, gaussians, views, view_projs, B, V, N, bg, limit):
+        """Everything of one batched pass before its blend, for the renderer and for GaussianFitter: fills ``p`` (GsBatchParams) from
+        contiguous fp32 device tensors (gaussians [B, N, 14], views / view_projs [B * V, 16]), runs the preprocess, reads the instance
+        total, and sizes and attaches the binning buffers.  -> (n, ok): the total, and whether it is within ``limit``; nothing is
+        attached when it is not."""
         device = gaussians.device
-        B, V = cam_view.shape[:2]
-        N, S = gaussians.shape[1], self.size
         lib = L.load()
         buf = self._batch_buffers(B, V, N, device)
-        g = gaussians.float().contiguous()
-        views = cam_view.to(device, torch.float32).reshape(B * V, 16).contiguous()
-        vps = cam_view_proj.to(device, torch.float32).reshape(B * V, 16).contiguous()
-        dp = L.GsDepthParams()
-        p = dp.pass_
-        p.gaussians, p.B, p.N, p.V, p.size = g.data_ptr(), B, N, V, S
-        p.views, p.view_projs, p.tan_half_fov = views.data_ptr(), vps.data_ptr(), self.tan_half_fov
+        p.gaussians, p.B, p.N, p.V, p.size = gaussians.data_ptr(), B, N, V, self.size
+        p.views, p.view_projs, p.tan_half_fov = views.data_ptr(), view_projs.data_ptr(), self.tan_half_fov
         p.bg[0], p.bg[1], p.bg[2] = bg
-        p.depth, p.xy, p.conic_opacity, p.rect = buf["depth"].data_ptr(), buf["xy"].data_ptr(), buf["co"].data_ptr(), buf["rect"].data_ptr()
-        p.tiles_touched, p.offsets = buf["touched"].data_ptr(), buf["offsets"].data_ptr()
-        p.scan_temp, p.scan_temp_bytes = buf["scan"].data_ptr(), buf["scan"].numel()
+        self._attach_preprocess(p, buf)
         L.check(lib.vmv_gs_batch_preprocess(C.byref(p), _stream_ptr()), "gs_batch_preprocess")
         # the ONE host round trip of the call: the instance total sizes the sort (pinned destination: a 4-byte copy + stream sync)
         buf["total"].copy_(buf["offsets"][B * V * N - 1:], non_blocking=True)
@@ -163,24 +172,28 @@ class GaussianRenderer:
         n = int(buf["total"][0])
         # The scan and `num_rendered` are int32.  The caller bounds B * V * N * tiles below 2^32, so a total past 2^31 - 1 shows up as a
         # NEGATIVE count (never as a small positive one): refuse it, and refuse totals whose key / value buffers (24 B per instance,
-        # x 1.25 head-room) would pass the memory budget — the caller then splits the views.
-        if n < 0 or n > self.max_batch_instances:
+        # x 1.25 head-room) would pass the caller's budget.
+        if n < 0 or n > limit:
+            return n, False
+        self._attach_instances(p, buf, n, device, lambda cap, sb, so: lib.vmv_gs_batch_workspace_bytes(B * V * N, cap, buf["bits"], sb, so))
+        return n, True
+
+    def _render_batch(self, gaussians, cam_view, cam_view_proj, bg, images, alphas, depths=None, medians=None):
+        """All B * V views in one pass (vmv.h VmvGsBatchParams); with ``depths`` / ``medians`` the blend is the depth mode's
+        (VmvGsDepthParams: the same pass, the same image and alpha bits).  -> False when the instance total passes
+        ``max_batch_instances``: the caller then splits the views."""
+        device = gaussians.device
+        B, V = cam_view.shape[:2]
+        lib = L.load()
+        g = gaussians.float().contiguous()
+        views = cam_view.to(device, torch.float32).reshape(B * V, 16).contiguous()
+        vps = cam_view_proj.to(device, torch.float32).reshape(B * V, 16).contiguous()
+        dp = L.GsDepthParams()
+        p = dp.pass_
+        n, ok = self._batch_setup(p, g, views, vps, B, V, gaussians.shape[1], bg, self.max_batch_instances)
+        if not ok:
             return False
         self.last_num_rendered.append(n)
-        if n > buf["cap"]:
-            cap = max(int(n * 1.25), 1 << 16)
-            sb, so = C.c_size_t(0), C.c_size_t(0)
-            L.check(lib.vmv_gs_batch_workspace_bytes(B * V * N, cap, buf["bits"], C.byref(sb), C.byref(so)), "gs_batch_workspace_bytes")
-            i64 = lambda: torch.zeros(cap, dtype=torch.int64, device=device)
-            i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=device)
-            buf.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
-                       sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=device))
-        p.num_rendered = n
-        if n > 0:
-            p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(), buf["vals"].data_ptr(),
-                                                            buf["vals_s"].data_ptr())
-            p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
-        p.ranges = buf["ranges"].data_ptr()
         p.out_color, p.out_alpha = images.data_ptr(), alphas.data_ptr()
         if depths is None:
             L.check(lib.vmv_gs_batch_render(C.byref(p), _stream_ptr()), "gs_batch_render")
@@ -247,7 +260,8 @@ class GaussianRenderer:
             if self._render_views(gaussians, cam_view, cam_view_proj, bg, images, alphas):
                 return {"image": images, "alpha": alphas}
         buf = self._buffers(N, device)
-        self.last_num_rendered, self.last_views = [], B * V
+        self.last_num_rendered = []           # (drops the chunks a batched attempt rendered before one view was refused)
+        workspace_bytes = lambda cap, sb, so: lib.vmv_gs_workspace_bytes(N, cap, sb, so)
         for b in range(B):
             g = gaussians[b].float().contiguous()
             for v in range(V):
@@ -257,20 +271,11 @@ class GaussianRenderer:
                 p.gaussians, p.N, p.size, p.view, p.view_proj = g.data_ptr(), N, S, view.data_ptr(), vp.data_ptr()
                 p.tan_half_fov = self.tan_half_fov
                 p.bg[0], p.bg[1], p.bg[2] = bg
-                p.depth, p.xy, p.conic_opacity, p.rect = (buf["depth"].data_ptr(), buf["xy"].data_ptr(), buf["co"].data_ptr(),
-                                                          buf["rect"].data_ptr())
-                p.tiles_touched, p.offsets = buf["touched"].data_ptr(), buf["offsets"].data_ptr()
-                p.scan_temp, p.scan_temp_bytes = buf["scan"].data_ptr(), buf["scan"].numel()
+                self._attach_preprocess(p, buf)
                 L.check(lib.vmv_gs_preprocess(C.byref(p), _stream_ptr()), "gs_preprocess")
                 n = int(buf["offsets"][N - 1].item())                       # the one host round trip per view
                 self.last_num_rendered.append(n)
-                self._grow(buf, N, n, device)
-                p.num_rendered = n
-                if n > 0:
-                    p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(),
-                                                                    buf["vals"].data_ptr(), buf["vals_s"].data_ptr())
-                    p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
-                p.ranges = buf["ranges"].data_ptr()
+                self._attach_instances(p, buf, n, device, workspace_bytes)
                 p.out_color, p.out_alpha = images[b, v].data_ptr(), alphas[b, v].data_ptr()
                 L.check(lib.vmv_gs_render(C.byref(p), _stream_ptr()), "gs_render")
         return {"image": images, "alpha": alphas}

@@ -155,41 +155,16 @@ class GaussianFitter:
 
     def _forward(self):
         """Preprocess, size the instance buffers (one host read), forward with state.  -> the backward's argument block."""
-        lib, r = L.load(), self.renderer
-        B, V, N, S = self.B, self.V, self.N, self.S
-        buf = r._batch_buffers(B, V, N, self.device)
         q = L.GsBackwardParams()
         p = q.pass_
-        p.gaussians, p.B, p.N, p.V, p.size = self.gs.data_ptr(), B, N, V, S
-        p.views, p.view_projs, p.tan_half_fov = self.views.data_ptr(), self.view_projs.data_ptr(), r.tan_half_fov
-        p.bg[0], p.bg[1], p.bg[2] = self.bg
-        p.depth, p.xy, p.conic_opacity, p.rect = buf["depth"].data_ptr(), buf["xy"].data_ptr(), buf["co"].data_ptr(), buf["rect"].data_ptr()
-        p.tiles_touched, p.offsets = buf["touched"].data_ptr(), buf["offsets"].data_ptr()
-        p.scan_temp, p.scan_temp_bytes = buf["scan"].data_ptr(), buf["scan"].numel()
-        L.check(lib.vmv_gs_batch_preprocess(C.byref(p), _stream_ptr()), "gs_batch_preprocess")
-        buf["total"].copy_(buf["offsets"][B * V * N - 1:], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        n = int(buf["total"][0])
-        if n < 0 or n > (1 << 28):
+        n, ok = self.renderer._batch_setup(p, self.gs, self.views, self.view_projs, self.B, self.V, self.N, self.bg, 1 << 28)
+        if not ok:
             raise RuntimeError(f"GaussianFitter: {n} instances — too many for one pass (fewer views or a smaller image)")
-        if n > buf["cap"]:
-            cap = max(int(n * 1.25), 1 << 16)
-            sb, so = C.c_size_t(0), C.c_size_t(0)
-            L.check(lib.vmv_gs_batch_workspace_bytes(B * V * N, cap, buf["bits"], C.byref(sb), C.byref(so)), "gs_batch_workspace_bytes")
-            i64 = lambda: torch.zeros(cap, dtype=torch.int64, device=self.device)
-            i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=self.device)
-            buf.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
-                       sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=self.device))
-        self.num_rendered = p.num_rendered = n
-        if n > 0:
-            p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(), buf["vals"].data_ptr(),
-                                                            buf["vals_s"].data_ptr())
-            p.sort_temp, p.sort_temp_bytes = buf["sort"].data_ptr(), buf["sort"].numel()
-        p.ranges = buf["ranges"].data_ptr()
+        self.num_rendered = n
         p.out_color, p.out_alpha = self.image.data_ptr(), self.alpha.data_ptr()
         q.final_T, q.n_contrib = self.final_T.data_ptr(), self.n_contrib.data_ptr()
         q.dL_dimage, q.grad2d, q.grad_view, q.grad = self.dL.data_ptr(), self.grad2d.data_ptr(), self.grad_view.data_ptr(), self.grad.data_ptr()
-        L.check(lib.vmv_gs_batch_render_state(C.byref(q), _stream_ptr()), "gs_batch_render_state")
+        L.check(L.load().vmv_gs_batch_render_state(C.byref(q), _stream_ptr()), "gs_batch_render_state")
         return q
 
     def _loss(self, with_grad=True):
