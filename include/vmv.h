@@ -45,7 +45,7 @@ int vmv_has_experiments(void);
 /* sizeof() of the argument blocks, so a foreign-language binding can verify its struct layout:
  * which = VMV_OP_* (GN_STATS/GN_APPLY share a block), 100 = VmvDdimParams, 101 = VmvGemmSeg, 102 = VmvSeqMap,
  * 103 = VmvGsParams, 104 = VmvGsBatchParams, 105 = VmvGsBackwardParams, 106 = VmvGsAdamParams, 107 = VmvGsSsimLossParams,
- * 108 = VmvGsDepthParams, 109 = VmvGsTsdfParams */
+ * 108 = VmvGsDepthParams, 109 = VmvGsTsdfParams, 110 = VmvGsMeshComponentsParams */
 int vmv_sizeof(int which);
 /* human-readable text for a code returned by any launcher (VMV_E* or hipError_t) */
 const char* vmv_error_string(int code);
@@ -695,6 +695,33 @@ typedef struct {
     long  plane_stride;        /*   0 sum tsdf, 1 W, 2 n_behind, 3..5 sum R G B, 6 Wc;   plane_stride >= R^3 (floats)       */
 } VmvGsTsdfParams;
 int vmv_gs_tsdf_integrate(const VmvGsTsdfParams* p, void* stream);   /* vmv_sizeof(109) */
+
+/* Connected components of a triangle mesh (csrc/gs_mesh_cc.hip; videomv_amd/gs_mesh.py: mesh_components, drop_small_components).
+ * Additive: the ABI version does not change, callers detect the entry by its symbol.
+ *   label[v]      = the smallest vertex index of the component that holds v.  Two vertices share a component iff a chain of faces
+ *                   connects them; a vertex in no face is its own component.
+ *   face_count[r] = the number of faces of the component whose label is r, 0 at every other index.
+ * The result is canonical: it depends on neither the order of the faces, their winding, nor the order in which threads run, so two
+ * calls give the same bits.  A degenerate face (a, a, b) counts and connects what it names; a duplicate face counts each time.
+ * A face with any index outside [0, n_vertices) is skipped whole, neither connected nor counted (the range test comes before any
+ * access that uses the index), and sets bit 0 of *status.  Bit 1 of *status: a bounded loop of the union-find gave up (the parent
+ * array, which lives in ``label`` during the call, was written by something else); the outputs are then not the components.
+ * The call initialises all three outputs itself, on ``stream``: init (label[i] = i, counts 0, status 0), hook (one thread per face:
+ * union (v0, v1) and (v0, v2), always the larger root under the smaller, so parent[i] <= i at every instant), flatten
+ * (label[i] = root(i)), count (integer atomic adds).  n_faces == 0 is valid: identity labels, zero counts.
+ * Argument checks run before any launch and need no device: VMV_ENULL (p, faces, label, face_count or status null), VMV_EINVAL
+ * (n_vertices < 1, n_faces < 0, face_stride < 3), VMV_ERANGE (n_vertices or n_faces beyond int32), VMV_EALIGN (faces not 8-byte
+ * aligned, an int32 pointer not 4-byte aligned).  No allocation, no synchronisation. */
+typedef struct {
+    const int64_t* faces;      /* [n_faces] triples of vertex indices, face f at faces + f * face_stride (what surface_nets returns) */
+    int64_t  face_stride;      /* elements from one face to the next, >= 3                                                   */
+    int64_t  n_faces;          /* >= 0                                                                                       */
+    int64_t  n_vertices;       /* >= 1                                                                                       */
+    int32_t* label;            /* out [n_vertices]                                                                           */
+    int32_t* face_count;       /* out [n_vertices]                                                                           */
+    int32_t* status;           /* out [1]: bit 0 a face index out of range, bit 1 a bounded loop gave up                     */
+} VmvGsMeshComponentsParams;
+int vmv_gs_mesh_components(const VmvGsMeshComponentsParams* p, void* stream);   /* vmv_sizeof(110) */
 
 /* ------------------------------------------------------------------------------------------------------
  * Block permute-copy (frame-sharded sampling, DESIGN.md §8: packs / unpacks the all-to-all buffers that switch an

@@ -5,8 +5,15 @@ replaces: a torch-eager formulation of the same definition on the same GPU in th
 volume (it states the alternative; it is not a target).  Medians over --iters calls after --warmup.  Rates: the depth gathers the
 kernel issues (R^3 V, one per voxel and view) per second, and the plane bytes it moves (7 planes x R^3 x 4 B, read and written) per
 second.  Prints one JSON line per shape; --log FILE appends them to FILE.
-    python tools/gs_mesh_bench.py [--shapes 128:24:256,256:48:512] [--iters 30] [--warmup 5] [--gaussians 65536]"""
+    python tools/gs_mesh_bench.py [--shapes 128:24:256,256:48:512] [--iters 30] [--warmup 5] [--gaussians 65536]
+--components measures the component labelling instead (csrc/gs_mesh_cc.hip), on the meshes extracted at those shapes and on a strip of
+65 536 triangles numbered by a seeded permutation: the median ms of one vmv_gs_mesh_components call into preallocated outputs, of the
+eager propagation that is gs_mesh.mesh_components' CPU fallback run on the device in the same process (the yardstick; it states the
+alternative), and of gs_mesh.drop_small_components (labelling, status read-back, masks and the remap).  Appends to
+profiles/gs_mesh_cc_bench.log unless --log names another file.
+    python tools/gs_mesh_bench.py --components [--shapes ...] [--iters 30] [--warmup 5]"""
 import argparse
+import ctypes as C
 import json
 import math
 import os
@@ -47,6 +54,32 @@ def eager_integrate(acc, depth, colour, views, tan, origin, voxel, trunc, z_min,
             acc[6] += near
 
 
+def components_record(name, verts, cols, faces, iters, warmup):
+    """-> the JSON record of one mesh: kernel, eager propagation and floater filter, and that the first two agree"""
+    from videomv_amd import _lib as L
+    from videomv_amd.gs_mesh import _components_eager, drop_small_components
+    from videomv_amd.ops import _stream_ptr
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    faces = faces.contiguous()
+    out = torch.empty(2 * n + 1, dtype=torch.int32, device="cuda")
+    p = L.GsMeshComponentsParams()
+    p.faces, p.face_stride, p.n_faces, p.n_vertices = faces.data_ptr(), 3, m, n
+    p.label, p.face_count, p.status = out.data_ptr(), out.data_ptr() + 4 * n, out.data_ptr() + 8 * n
+    lib, stream = L.load(), _stream_ptr()
+    hip = median_ms(lambda: L.check(lib.vmv_gs_mesh_components(C.byref(p), stream), "gs_mesh_components"), iters, warmup)
+    label, count, status = out[:n].long(), out[n:2 * n].long(), int(out[2 * n])
+    res = {}
+    eager = median_ms(lambda: res.update(e=_components_eager(faces, n)), max(3, iters // 3), 1)
+    drop = median_ms(lambda: res.update(d=drop_small_components(verts, cols, faces, min_fraction=0.05)), max(3, iters // 3), 1)
+    sizes = count[count > 0].sort(descending=True).values
+    r3 = lambda t: [round(x, 4) for x in t]
+    return dict(mesh=name, vertices=n, faces=m, components=int((label == torch.arange(n, device="cuda")).sum()),
+                largest_components=sizes[:6].tolist(), status=status, components_ms=r3(hip), eager_ms=r3(eager), drop_ms=r3(drop),
+                ms_are="median, min, max", eager_over_hip=round(eager[0] / hip[0], 2),
+                agrees_with_eager=bool(torch.equal(label, res["e"][0]) and torch.equal(count, res["e"][1])),
+                dropped=res["d"][3])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="128:24:256,256:48:512", help="R:V:S, comma-separated")
@@ -54,7 +87,10 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--gaussians", type=int, default=65536)
     ap.add_argument("--log", default=None)
+    ap.add_argument("--components", action="store_true", help="measure the component labelling on the extracted meshes instead")
     args = ap.parse_args(argv)
+    if args.components and not args.log:
+        args.log = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gs_mesh_cc_bench.log")
 
     def emit(rec):
         line = json.dumps(rec)
@@ -74,6 +110,11 @@ def main(argv=None):
         depth, colour = out["median_depth"][0, :, 0].contiguous(), _unpremultiplied(out, 0.5).contiguous()
         views = cv.cuda()
         half = 2.0 * math.sin(0.5 * math.radians(r.fovy))
+        if args.components:
+            vol = TsdfVolume(R, half)
+            vol.integrate(depth, views, r.tan_half_fov, colour=colour)
+            emit(components_record(f"extract R={R} V={V} S={S}", *vol.extract(), args.iters, args.warmup))
+            continue
         vol = TsdfVolume(R, half)
         hip = median_ms(lambda: vol.integrate(depth, views, r.tan_half_fov, colour=colour), args.iters, args.warmup)
         # one call each from zero: the mesh, and the eager formulation's planes against the kernel's
@@ -98,6 +139,12 @@ def main(argv=None):
                   map_bytes=int(depth.numel() * 4 + colour.numel() * 4), plane_bytes=7 * n * 4 * 2,
                   extract_ms=r3(ext), mesh=dict(vertices=st["vertices"], faces=st["faces"], open_edges=st["open_edges"], euler=st["euler"]),
                   counts_that_differ_from_eager=differ, tsdf_max_diff_vs_eager=float((acc[0] - vol.acc[0]).abs().max())))
+    if args.components:
+        T = 65536
+        i = torch.arange(T)
+        strip = torch.randperm(T + 2, generator=torch.Generator().manual_seed(11))[torch.stack([i, i + 1, i + 2], dim=1)].cuda()
+        v = torch.zeros(T + 2, 3, device="cuda")
+        emit(components_record("strip of 65536 triangles, permuted numbering", v, v, strip, args.iters, args.warmup))
 
 
 if __name__ == "__main__":

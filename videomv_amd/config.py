@@ -80,6 +80,8 @@ def default_cfg() -> AttrDict:
     c.gs_mesh_res = 128               # voxels per side of the fusion volume, 16 .. 512
     c.gs_mesh_extent = None           # half-width of its cube (None: d sin(fovy / 2), the ball every orbit view sees whole)
     c.gs_mesh_trunc = None            # truncation distance of the TSDF (None: 3 voxels)
+    c.gs_mesh_min_component = None    # drop the mesh's connected components with fewer faces than this fraction [0, 1] of the largest (None: keep all)
+    c.gs_mesh_elevations = None       # extra elevations in degrees, each inside (-90, 90): one more orbit of gs_orbit_views fused per value (None: none)
     return c
 
 

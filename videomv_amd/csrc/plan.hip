@@ -61,6 +61,7 @@ extern "C" int vmv_sizeof(int which) {
         case 107: return (int)sizeof(VmvGsSsimLossParams);
         case 108: return (int)sizeof(VmvGsDepthParams);
         case 109: return (int)sizeof(VmvGsTsdfParams);
+        case 110: return (int)sizeof(VmvGsMeshComponentsParams);
         default: return (int)op_size(which);
     }
 }

@@ -403,7 +403,7 @@ def _check_export_cfg(cfg, use_lgm):
     if cfg.get('gs_points_voxel') is not None and cfg.get('gs_points') and not float(cfg.get('gs_points_voxel')) > 0:
         raise ValueError(f"gs_points_voxel must be positive, got {cfg.get('gs_points_voxel')}")
     if not cfg.get('gs_mesh'):
-        sub = [k for k in ('gs_mesh_extent', 'gs_mesh_trunc') if cfg.get(k) is not None]
+        sub = [k for k in ('gs_mesh_extent', 'gs_mesh_trunc', 'gs_mesh_min_component', 'gs_mesh_elevations') if cfg.get(k) is not None]
         sub += ['gs_mesh_res'] if int(cfg.get('gs_mesh_res') or 128) != 128 else []
         if sub:
             raise ValueError(f"{' / '.join(sub)}: a setting of the gs_mesh export: set gs_mesh True")
@@ -413,6 +413,13 @@ def _check_export_cfg(cfg, use_lgm):
         for k in ('gs_mesh_extent', 'gs_mesh_trunc'):
             if cfg.get(k) is not None and not float(cfg.get(k)) > 0:
                 raise ValueError(f"{k} must be positive, got {cfg.get(k)}")
+        frac = cfg.get('gs_mesh_min_component')
+        if frac is not None and not (_is_number(frac) and 0.0 <= float(frac) <= 1.0):
+            raise ValueError(f"gs_mesh_min_component must be a fraction in [0, 1] of the largest component's faces, got {frac!r}")
+        elevs = cfg.get('gs_mesh_elevations')
+        if elevs is not None and not (isinstance(elevs, (list, tuple))
+                                      and all(_is_number(e) and math.isfinite(float(e)) and -90.0 < float(e) < 90.0 for e in elevs)):
+            raise ValueError(f"gs_mesh_elevations must be a list of elevations in degrees inside (-90, 90), got {elevs!r}")
     if not cfg.get('save_gaussians'):
         return
     if not use_lgm:
@@ -424,6 +431,10 @@ def _check_export_cfg(cfg, use_lgm):
         check_loss(*_fit_loss(cfg))
     except ValueError as e:
         raise ValueError(f"save_gaussians: gs_fit_loss / gs_fit_lambda_dssim: {e}") from None
+
+
+def _is_number(x):
+    return isinstance(x, (int, float)) and not isinstance(x, bool)
 
 
 def _fit_loss(cfg):
@@ -439,7 +450,9 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
     ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit; with ``gs_orbit_depth``
     / ``gs_points`` / ``gs_mesh`` that orbit is rendered ONCE in the rasteriser's depth mode and its median-depth maps
     (``_gs_orbit_depth.npy`` / ``.png``), the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) and the coloured
-    triangle mesh they fuse to (``_gs_mesh.ply``: TSDF fusion + surface nets on the device, gs_mesh.py) are written too.  Draws nothing from
+    triangle mesh they fuse to (``_gs_mesh.ply``: TSDF fusion + surface nets on the device, gs_mesh.py) are written too;
+    ``gs_mesh_elevations`` fuses one more orbit per extra elevation into that mesh (rendered for the fusion alone: no file shows them) and
+    ``gs_mesh_min_component`` drops its small connected components before it is written.  Draws nothing from
     the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
     from .gs import GaussianRenderer
     from .lgm import orbit_cameras
@@ -496,19 +509,32 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
             rec['points'] = _export_points(out, cv[0], renderer.tan_half_fov, refiner.bg_color, voxel, rec['points_ply'])
             logging.info(f"Save point cloud ({rec['points']} points, voxel {voxel:.5f}) to {rec['points_ply']}")
         if cfg.get('gs_mesh'):
-            from .gs_mesh import TsdfVolume, mesh_stats, save_mesh_ply
+            from .gs_mesh import TsdfVolume, drop_small_components, mesh_stats, save_mesh_ply
             res, half, trunc = int(cfg.get('gs_mesh_res') or 128), cfg.get('gs_mesh_extent'), cfg.get('gs_mesh_trunc')
             # default cube: the ball every orbit view sees whole, d sin(fovy / 2) around the origin of the Gaussians' frame
             cam_dist = float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
             half = cam_dist * math.sin(0.5 * math.radians(opt.fovy)) if half is None else float(half)
             vol = TsdfVolume(res, half, trunc=None if trunc is None else float(trunc), device=device)
             vol.integrate(out["median_depth"][0, :, 0], cv[0], renderer.tan_half_fov, colour=_unpremultiplied(out, refiner.bg_color))
+            # one more orbit per extra elevation, at the same distance (the default cube is the ball seen whole from that distance, at
+            # any elevation): rendered for the fusion alone
+            for extra in cfg.get('gs_mesh_elevations') or []:
+                cv_e, cvp_e = orbit_cameras(camera_data, n_orbit, float(extra), camera_dist, opt)
+                out_e = renderer.render_depth(g.to(device), cv_e.to(device), cvp_e.to(device), None, bg_color=bgc)
+                vol.integrate(out_e["median_depth"][0, :, 0], cv_e[0], renderer.tan_half_fov, colour=_unpremultiplied(out_e, refiner.bg_color))
+            rec['mesh_fused_views'] = vol.n_views
             verts, cols, faces = vol.extract()
+            dropped = ""
+            if cfg.get('gs_mesh_min_component') is not None:
+                verts, cols, faces, info = drop_small_components(verts, cols, faces, min_fraction=float(cfg.get('gs_mesh_min_component')))
+                rec['mesh_components'], rec['mesh_components_dropped'] = info['components'], info['components'] - info['kept']
+                dropped = (f"; {info['components']} components, {rec['mesh_components_dropped']} dropped with {info['dropped_faces']} faces "
+                           f"and {info['dropped_vertices']} vertices")
             rec['mesh_ply'] = stem + '_gs_mesh.ply'
             rec['mesh_vertices'], rec['mesh_faces'] = save_mesh_ply(verts, cols, faces, rec['mesh_ply'])
             rec['mesh_open_edges'] = mesh_stats(verts, faces)['open_edges']
             logging.info(f"Save mesh ({rec['mesh_vertices']} vertices, {rec['mesh_faces']} faces, {rec['mesh_open_edges']} open edges; "
-                         f"{res}^3 voxels of {vol.voxel:.5f}, {n_orbit} views fused) to {rec['mesh_ply']}")
+                         f"{res}^3 voxels of {vol.voxel:.5f}, {rec['mesh_fused_views']} views fused{dropped}) to {rec['mesh_ply']}")
     return rec
 
 

@@ -3,8 +3,10 @@ and naive surface nets over the fused field, in vectorised torch on the device t
 
 ``TsdfVolume`` owns the seven accumulator planes of ``VmvGsTsdfParams`` and turns them into a signed field; ``surface_nets`` places one
 vertex per sign-changing cell and one quad per sign-changing grid edge; ``mesh_stats`` counts what a consumer would trip over (open and
-misoriented edges, the Euler characteristic, the signed volume); ``save_mesh_ply`` / ``load_mesh_ply`` are the binary little-endian
-writer and its inverse.  No RNG anywhere: the same inputs give the same file.
+misoriented edges, the Euler characteristic, the signed volume); ``mesh_components`` labels the connected components of a mesh
+(``csrc/gs_mesh_cc.hip`` on the device, a torch propagation on the CPU) and ``drop_small_components`` removes the floaters among them;
+``save_mesh_ply`` / ``load_mesh_ply`` are the binary little-endian writer and its inverse.  No RNG anywhere: the same inputs give the
+same file.
 """
 import ctypes as C
 
@@ -155,6 +157,81 @@ def mesh_stats(verts, faces):
     return dict(vertices=int(v.shape[0]), edges=E, faces=int(f.shape[0]), euler=int(v.shape[0]) - E + int(f.shape[0]),
                 open_edges=int((uc != 2).sum()), misoriented=int((dc > 1).sum()),
                 volume=float((a * torch.linalg.cross(b, c)).sum() / 6.0))
+
+
+def _components_eager(faces, n):
+    """The contract of ``mesh_components`` in torch, on faces' device: every round gives each vertex of a face, and the vertex its label
+    names, the smallest label of the face (scatter amin), then jumps label <- label[label] twice; repeated until a round changes nothing.
+    A label always names a vertex of the same component and never exceeds its own index, so the fixed point — constant on every face,
+    hence on every component — is the component's smallest index.  ``faces`` [m, 3] in range.  -> (label, face_count) [n] int64."""
+    label = torch.arange(n, dtype=torch.int64, device=faces.device)
+    flat = faces.reshape(-1)
+    while flat.numel():
+        low = label[faces].min(dim=1).values.repeat_interleave(3)
+        new = label.scatter_reduce(0, flat, low, "amin").scatter_reduce(0, label[flat], low, "amin")
+        new = new[new]
+        new = new[new]
+        if torch.equal(new, label):
+            break
+        label = new
+    count = torch.zeros(n, dtype=torch.int64, device=faces.device)
+    if flat.numel():
+        count.index_add_(0, label[faces[:, 0]], torch.ones_like(faces[:, 0]))
+    return label, count
+
+
+@torch.no_grad()
+def mesh_components(faces, n_vertices):
+    """Connected components of the mesh ``faces`` [m, 3] (int64) over ``n_vertices`` vertices -> (label [n] int64, face_count [n] int64):
+    label[v] is the smallest vertex index of v's component (a vertex in no face is its own), face_count[r] the number of faces of the
+    component labelled r and 0 elsewhere (the contract of vmv_gs_mesh_components, include/vmv.h).  CUDA tensors run the kernel on the
+    current stream; CPU tensors the torch propagation above.  A face index outside [0, n_vertices) raises ValueError."""
+    n, m = int(n_vertices), int(faces.shape[0])
+    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64 and n >= 0
+    out_of_range = f"mesh_components: a face names a vertex outside [0, {n})"
+    if n == 0:
+        if m:
+            raise ValueError(out_of_range)
+        return (torch.zeros(0, dtype=torch.int64, device=faces.device),) * 2
+    if not faces.is_cuda:
+        if m and bool(((faces < 0) | (faces >= n)).any()):
+            raise ValueError(out_of_range)
+        return _components_eager(faces, n)
+    from .ops import _stream_ptr
+    if m and not (faces.stride(1) == 1 and faces.stride(0) >= 3):
+        faces = faces.contiguous()
+    out = torch.empty(2 * n + 1, dtype=torch.int32, device=faces.device)
+    p = L.GsMeshComponentsParams()
+    p.faces = faces.data_ptr() if m else out.data_ptr()                 # no face is read when there is none
+    p.face_stride, p.n_faces, p.n_vertices = (int(faces.stride(0)) if m else 3), m, n
+    p.label, p.face_count, p.status = out.data_ptr(), out.data_ptr() + 4 * n, out.data_ptr() + 8 * n
+    L.check(L.load().vmv_gs_mesh_components(C.byref(p), _stream_ptr()), "gs_mesh_components")
+    status = int(out[2 * n])
+    if status & 2:
+        raise RuntimeError("mesh_components: a bounded loop of the union-find gave up (status bit 1): the label buffer was written during the call")
+    if status & 1:
+        raise ValueError(out_of_range)
+    return out[:n].long(), out[n:2 * n].long()
+
+
+@torch.no_grad()
+def drop_small_components(verts, colours, faces, min_fraction=0.0, min_faces=0):
+    """Remove the small connected components (floaters) of a mesh.  A component is kept iff its face count is >= ``min_faces`` and
+    >= ``min_fraction`` x the largest component's face count; kept vertices and kept faces keep their order, indices are remapped; with
+    both thresholds 0 everything is kept.  Runs on the tensors' device, draws no RNG.
+    -> (verts, colours, faces, info) with info = dict(components, kept, largest_faces, dropped_faces, dropped_vertices)."""
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    label, count = mesh_components(faces, n)
+    is_root = label == torch.arange(n, dtype=torch.int64, device=label.device)
+    largest = int(count.max()) if n else 0
+    keep_root = is_root & (count >= int(min_faces)) & (count.double() >= float(min_fraction) * largest)
+    keep_v = keep_root[label]
+    keep_f = keep_v[faces[:, 0]]
+    remap = torch.cumsum(keep_v, 0) - 1
+    out_faces = remap[faces[keep_f]]
+    info = dict(components=int(is_root.sum()), kept=int(keep_root.sum()), largest_faces=largest,
+                dropped_faces=m - int(out_faces.shape[0]), dropped_vertices=n - int(keep_v.sum()))
+    return verts[keep_v], colours[keep_v], out_faces, info
 
 
 _VERTEX = [("xyz", "<f4", 3), ("rgb", "u1", 3)]                         # 15 bytes
