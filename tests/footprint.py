@@ -685,6 +685,95 @@ def permute_copy_case():
     return FCase("permute_copy", a, {}, build, I.permute_copy, lambda lib, p, st: lib.vmv_permute_copy(C.byref(p), st), {"dst": "exact"})
 
 
+def _whole(b, k):
+    """[rows][ld] host view of arena k from the kernel's pointer (col_off = 0)"""
+    a = b.case.arenas[k]
+    return b.buf(k).view(-1, a.ld)[a.gb:a.gb + a.rows]
+
+
+F32_TOL = dict(tol_l2=1e-3, tol_max=2e-3)          # fp32 in, fp32 out: as the fp32-output GEMM cases (the fp64 comparison is tests/test_glue_gpu.py)
+
+
+def cfg_ddim_case():
+    """eps rows of stride C + 4 (NaN pad); xt (in place), x0_out and noise dense [C][F * HW] between guard rows; clamp and sigma > 0"""
+    Cc, F_, HW = 4, 3, 37
+    FHW, ld = F_ * HW, Cc + 4
+    kw = dict(guide_scale=9.0, c_recip=1.31, c_recipm1=0.85, c_sqrt_ac=0.76, c_sqrt_1mac=0.65, a_prev=0.71, clamp=1.1, sigma=0.2)
+    a = {"eps": Arena(2 * FHW, Cc, "f32", ld=ld, poison="nan", data=rnd((2 * FHW, Cc), 2)), "xt": Arena(Cc, FHW, "f32", data=rnd((Cc, FHW), 1)),
+         "x0": Arena(Cc, FHW, "f32"), "noise": Arena(Cc, FHW, "f32", poison="nan", data=rnd((Cc, FHW), 5))}
+    sh = (1, Cc, F_, 1, HW)
+
+    def ref(b):
+        I.cfg_ddim_step(_whole(b, "eps"), ld, b.payload("xt").view(sh), x0_out=b.payload("x0").view(sh), noise=b.payload("noise").view(sh), **kw)
+
+    def gpu(lib, b, st):
+        p = L.DdimParams()
+        p.eps_rows, p.ld, p.C, p.F, p.HW = b["eps"], ld, Cc, F_, HW
+        p.guide_scale, p.c_recip, p.c_recipm1, p.c_sqrt_ac, p.c_sqrt_1mac, p.a_prev, p.v_pred = 9.0, 1.31, 0.85, 0.76, 0.65, 0.71, 0
+        p.xt, p.x0_out, p.clamp, p.sigma, p.noise = b["xt"], b["x0"], 1.1, 0.2, b["noise"]
+        return lib.vmv_cfg_ddim_step(C.byref(p), st)
+
+    return _glue("cfg_ddim_step", a, {}, ref, gpu, {"xt": F32_TOL, "x0": F32_TOL})
+
+
+def ddim_x0_case():
+    """xt updated in place between guard rows"""
+    n = 445
+    u = rnd((n,), 1)
+    a = {"xt": Arena(1, n, "f32", data=rnd((1, n), 3))}
+    dn = {"c": u + 0.3 * rnd((n,), 2), "u": u, "noise": rnd((n,), 4)}
+    args = (9.0, 1.31, 0.85, 0.71)
+    return _glue("ddim_x0_step", a, dn, lambda b: I.ddim_x0_step(b["c"], b["u"], b.payload("xt").view(n), *args, clamp=1.1, sigma=0.2, noise=b["noise"]),
+                 lambda lib, b, st: lib.vmv_ddim_x0_step(b["c"].data_ptr(), b["u"].data_ptr(), b["xt"], n, *args, 1.1, 0.2, b["noise"].data_ptr(), st), {"xt": F32_TOL})
+
+
+def posterior_case():
+    """moments rows of stride 2 zc + 4 (NaN pad)"""
+    n, zc, HW = 2, 4, 37
+    ld = 2 * zc + 4
+    mom = torch.cat([rnd((n * HW, zc), 1), 3.0 * rnd((n * HW, zc), 2)], dim=1)
+    a = {"mom": Arena(n * HW, 2 * zc, "f32", ld=ld, poison="nan", data=mom), "z": Arena(n * zc, HW, "f32")}
+    dn = {"noise": rnd((n, zc, 1, HW), 3)}
+    return _glue("posterior_sample", a, dn, lambda b: I.posterior_sample(_whole(b, "mom"), ld, b["noise"], b.payload("z").view(n, zc, 1, HW), 0.18215),
+                 lambda lib, b, st: lib.vmv_posterior_sample(b["mom"], ld, b["noise"].data_ptr(), b["z"], n, zc, HW, 0.18215, st), {"z": F32_TOL})
+
+
+def lgm_x0_views_case():
+    """eps rows of stride C + 4; NaN in the pad, in the frames idx4 does not name (eps and xt) and in the whole other branch"""
+    Cc, F_, HW, branch, idx4 = 4, 5, 37, 1, (4, 0, 2, 2)
+    ld = Cc + 4
+    eps = rnd((2, F_, HW, Cc), 1)
+    xt = rnd((1, Cc, F_, 1, HW), 2)
+    eps[1 - branch] = float("nan")
+    for f in range(F_):
+        if f not in idx4:
+            eps[:, f], xt[:, :, f] = float("nan"), float("nan")
+    a = {"eps": Arena(2 * F_ * HW, Cc, "f32", ld=ld, poison="nan", data=eps.reshape(-1, Cc)), "out": Arena(4 * Cc, HW, "f32")}
+    ia = (C.c_int32 * 4)(*idx4)
+    return _glue("lgm_x0_views", a, {"xt": xt},
+                 lambda b: I.lgm_x0_views(_whole(b, "eps"), ld, branch, b["xt"], idx4, 1.31, 0.85, 5.49, b.payload("out").view(4, Cc, 1, HW)),
+                 lambda lib, b, st: lib.vmv_lgm_x0_views(b["eps"], ld, branch, b["xt"].data_ptr(), Cc, F_, HW, ia, 1.31, 0.85, 5.49, b["out"], st), {"out": F32_TOL})
+
+
+def lgm_pack_input_case():
+    V, HW = 3, 37
+    a = {"dec": Arena(V * 3, HW, "f32", poison="nan", data=rnd((V * 3, HW), 1, 1.2)), "rays": Arena(V * 6, HW, "f32", poison="nan", data=rnd((V * 6, HW), 2)),
+         "out": Arena(V * 9, HW, "f32")}
+    return _glue("lgm_pack_input", a, {},
+                 lambda b: I.lgm_pack_input(b.payload("dec").view(V, 3, 1, HW), b.payload("rays").view(V, 6, 1, HW), b.payload("out").view(V, 9, 1, HW)),
+                 lambda lib, b, st: lib.vmv_lgm_pack_input(b["dec"], b["rays"], b["out"], V, HW, st), {"out": F32_TOL})
+
+
+def gaussian_activation_case():
+    """raw rows of stride 16 with NaN in columns 14 and 15; the workspace is guarded beyond its 4 floats per first-pass block"""
+    n = 600
+    blocks = (n + 255) // 256
+    a = {"raw": Arena(n, 14, "f32", ld=16, poison="nan", data=2.0 * rnd((n, 14), 11)), "out": Arena(n, 14, "f32"), "ws": Arena(1, 4 * blocks, "f32")}
+    return _glue("gaussian_activation", a, {}, lambda b: I.gaussian_activation(_whole(b, "raw"), 16, b.payload("out"), n, None),
+                 lambda lib, b, st: lib.vmv_gaussian_activation(b["raw"], 16, b["out"], n, b["ws"], st), {"out": F32_TOL})
+
+
 GLUE = {"adaptive_avgpool_rows": avgpool_case, "i2v_temporal_adapter": i2v_adapter_case, "latent_to_rows": lambda: latent_to_rows_case(False),
         "latent_to_rows_keep": lambda: latent_to_rows_case(True), "rows_to_nchw": rows_to_nchw_case, "emb_combine_silu": emb_combine_case,
-        "permute_copy": permute_copy_case}
+        "permute_copy": permute_copy_case, "cfg_ddim_step": cfg_ddim_case, "ddim_x0_step": ddim_x0_case, "posterior_sample": posterior_case,
+        "lgm_x0_views": lgm_x0_views_case, "lgm_pack_input": lgm_pack_input_case, "gaussian_activation": gaussian_activation_case}

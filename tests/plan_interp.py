@@ -435,7 +435,7 @@ def sinusoidal(t, out, n, dim):
     half = dim // 2
     freq = torch.pow(10000, -torch.arange(half).float() / half)
     s = torch.outer(t.float(), freq)
-    out.copy_(torch.cat([torch.cos(s), torch.sin(s)], dim=1).to(L.elem()))
+    out.copy_(torch.cat([torch.cos(s), torch.sin(s), torch.zeros(n, dim - 2 * half)], dim=1).to(L.elem()))      # an odd dim: the last column is 0 (util.py:187-188)
 
 
 def cfg_ddim_step(eps_rows, ld, xt, guide_scale, c_recip, c_recipm1, c_sqrt_ac, c_sqrt_1mac, a_prev, v_pred=False,

@@ -1392,6 +1392,8 @@ def test_layout_and_ddim_kernels():
     s_ref = torch.zeros(2, 320, dtype=BF)
     I.sinusoidal(t, s_ref, 2, 320)
     assert (s.cpu().float() - s_ref.float()).abs().max() < 2e-2     # sin/cos of ~1e3 rad: fp32 range reduction differs
+    from tests import glue_ref as G                                 # ... and against fp64 at the derived bound (tests/test_glue_gpu.py: 16 units of the angle + half an ulp)
+    G.check("sinusoidal", s, G.sinusoidal(t, 320), G.K["sinusoidal"], BF, L.elem_name())
 
 
 def test_i2v_frontend_kernels():
