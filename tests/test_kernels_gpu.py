@@ -561,7 +561,9 @@ def test_gemm_rejects_bad_arguments():
 # ------------------------------------------------------------------------------------------------- norms
 @pytest.mark.parametrize("rows,rps,C0,C1,silu,eps", [(6 * 80, 80, 320, 0, True, 1e-5), (2 * 3 * 64, 3 * 64, 64, 0, False, 1e-6),
                                                      (4 * 100, 100, 1280, 640, True, 1e-5), (2 * 1000, 1000, 32, 0, True, 1e-5),
-                                                     (3 * 50, 50, 2560, 0, True, 1e-5)])
+                                                     (3 * 50, 50, 2560, 0, True, 1e-5),
+                                                     (2 * 21, 21, 2048, 0, True, 1e-5),         # 256 slots per row exactly; chunks of 16 + 5 rows
+                                                     (2 * 13, 13, 3072, 1024, True, 1e-5)])     # C = 4096 (the limit), two passes over the slots
 def test_groupnorm(rows, rps, C0, C1, silu, eps):
     Cc = C0 + C1
     c = Case(x=rnd((rows, C0), 1) + 0.5, x1=rnd((rows, max(C1, 8)), 2, 2.0), gamma=1 + 0.1 * torch.randn(Cc, generator=g(3)),

@@ -17,10 +17,8 @@ namespace {
 // fixed point per value: an integer limb (quantum 1, |sum| < 2^63: fp16's largest squares times a whole sample fit) and a fraction
 // limb (quantum 2^-40), so a block's fp32 partial sum is represented exactly whether the activations are 1e-3 or 3e3 (round 2's
 // single limb had a fixed 2^-12 quantum: a group of 1e-3-sized activations lost its variance).  Integer addition
-// commutes: the totals are bitwise reproducible whatever the arrival order.  Record per (stat, group): GN_REC int64 =
-// { sum_hi, sumsq_hi, sum_lo, sumsq_lo, pilot (fp32 bits), pad x3 }, kept GN_NREP times (see the atomics below).
-constexpr int GN_REC = 8;
-constexpr int GN_NREP = 8;                      // replicas of a record: chunk c adds into replica c % 8 (below)
+// commutes: the totals are bitwise reproducible whatever the arrival order.  Record per (stat, group): VMV_GN_REC int64 =
+// { sum_hi, sumsq_hi, sum_lo, sumsq_lo, pilot (fp32 bits), pad x3 }, kept VMV_GN_NREP times (see the atomics below).
 constexpr float GN_LO = 1099511627776.0f;       // 2^40
 
 VMV_DEV void gn_add2(unsigned long long* rec, int which, float v) {
@@ -28,23 +26,82 @@ VMV_DEV void gn_add2(unsigned long long* rec, int which, float v) {
     atomicAdd(rec + which, (unsigned long long)(long long)fl);
     atomicAdd(rec + 2 + which, (unsigned long long)(long long)((v - fl) * GN_LO));
 }
-VMV_DEV float gn_pilot(const VmvGroupNormParams& p, long row, int c) {          // element (row, channel c) of the (two-source) input
+
+// ---- the parts the three GroupNorm kernels share
+// Column-slot geometry: a 256-thread block over rows of `slots` 16-byte column slots.  A thread keeps ONE slot column (cl, then every
+// TPR-th) and walks rows rl, rl + RPP, ...; with more than 256 slots per row every thread is a column lane and RPP = 1.
+struct GnSlots {
+    int TPR, RPP;                                // threads per row, rows per pass
+    __host__ __device__ explicit GnSlots(int slots) : TPR(slots < 256 ? slots : 256), RPP(256 / TPR) {}
+};
+struct GnLane : GnSlots {
+    int rl, cl;                                  // row lane, column lane
+    bool active;                                 // (256 % TPR threads have no row)
+    __device__ explicit GnLane(int slots) : GnSlots(slots), rl((int)threadIdx.x / TPR), cl((int)threadIdx.x - rl * TPR), active(rl < RPP) {}
+};
+// Channel c of the (two-source) input: row 0 of its column and the row pitch.
+struct GnSrc { const uint16_t* base; long ld; };
+VMV_DEV GnSrc gn_src(const VmvGroupNormParams& p, int c) {
     const bool first = c < p.C0;
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(first ? p.x : p.x1);
-    return elem_to_f32(b[row * (long)(first ? p.ld : p.ld1) + (first ? c : c - p.C0)]);
+    return {first ? reinterpret_cast<const uint16_t*>(p.x) + c : reinterpret_cast<const uint16_t*>(p.x1) + (c - p.C0),
+            first ? p.ld : p.ld1};
 }
+VMV_DEV float gn_pilot(const VmvGroupNormParams& p, long row, int c) {          // element (row, channel c)
+    const GnSrc s = gn_src(p, c);
+    return elem_to_f32(s.base[row * s.ld]);
+}
+// Row walk of one lane down its slot column: while U rows remain, U independent 16-byte loads in flight, then f(slot, row) in row
+// order; r is left at the first row not consumed, so walks of falling U chain (8 / 4 / 1).  f by VALUE: through a reference the
+// compiler contracts the statistics pass's products differently and its sums change in the last bits.  (The fused kernel's first
+// pass keeps its own loop: on this walk, whatever the index type, it lost registers or time — profiles/gn_family_ab.log.)
+template <int U, typename F>
+VMV_DEV void gn_walk(const uint16_t* base, long ld, long& r, long row_end, int RPP, F f) {
+    for (; r + (long)(U - 1) * RPP < row_end; r += (long)U * RPP) {
+        u32x4_t v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) v[k] = *reinterpret_cast<const u32x4_t*>(base + (r + (long)k * RPP) * ld);
+#pragma unroll
+        for (int k = 0; k < U; ++k) f(v[k], r + (long)k * RPP);
+    }
+}
+// scale[c] = rstd[g] * gamma[c0 + c], shift[c] = beta[c0 + c] - mean[g] * scale[c] for the n channels (whole groups) from c0 on
+VMV_DEV void gn_scale_shift(float* scale, float* shift, const float* s_mean, const float* s_rstd, const VmvGroupNormParams& p,
+                            int c0, int n, int cpg) {
+    for (int c = threadIdx.x; c < n; c += 256) {
+        const int g = c / cpg;
+        const float sc = s_rstd[g] * p.gamma[c0 + c];
+        scale[c] = sc;
+        shift[c] = p.beta[c0 + c] - s_mean[g] * sc;
+    }
+}
+// y = [silu](x * scale + shift) of one 16-byte slot, its 8 scale / shift pairs in registers
+struct GnAffine {
+    float a[8], b[8];
+    VMV_DEV GnAffine(const float* scale, const float* shift) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { a[e] = scale[e]; b[e] = shift[e]; }
+    }
+    template <bool SILU>
+    VMV_DEV u32x4_t apply(const u32x4_t& v) const {
+        float f[8];
+        unpack8(v, f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            f[e] = f[e] * a[e] + b[e];
+            if constexpr (SILU) f[e] = silu_f(f[e]);
+        }
+        return pack8(f);
+    }
+};
 
 __global__ __launch_bounds__(256) void gn_stats_kernel(const VmvGroupNormParams p, const int nchunk) {
     VMV_KERNEL_ENTER();
     extern __shared__ __attribute__((aligned(16))) float sh[];
     const int C = p.C0 + p.C1;
     const int CS = C >> 3;                       // 16-byte column slots per row
-    const int TPR = CS < 256 ? CS : 256;         // threads per row
-    const int RPP = 256 / TPR;                   // rows per pass
+    const GnLane L(CS);
+    const int RPP = L.RPP, rl = L.rl;
     const int tid = threadIdx.x;
-    const int rl = tid / TPR;                    // row lane
-    const int cl = tid - rl * TPR;               // column lane
-    const bool active = rl < RPP;
     const int stat = blockIdx.y, chunk = blockIdx.x;
     const long row0 = (long)stat * p.rows_per_stat + (long)chunk * p.chunk_rows;
     long row_end = row0 + p.chunk_rows;
@@ -53,52 +110,25 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const VmvGroupNormParams 
     float* lsum = sh;                            // [RPP][C]
     float* lsq = sh + RPP * C;
     float* pil = sh + 2 * RPP * C;               // [32] pilots of this stat group
-    const uint16_t* x0 = reinterpret_cast<const uint16_t*>(p.x);
-    const uint16_t* x1 = reinterpret_cast<const uint16_t*>(p.x1);
     const int cpg_ = C >> 5;
     if (tid < 32) pil[tid] = gn_pilot(p, (long)stat * p.rows_per_stat, tid * cpg_);
     __syncthreads();
-    for (int cs = cl; cs < CS; cs += TPR) {
+    for (int cs = L.cl; cs < CS; cs += L.TPR) {
         float s[8], q[8], pl[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; pl[e] = pil[(cs * 8 + e) / cpg_]; }
-        if (active) {
-            const int c = cs * 8;
-            const bool first = c < p.C0;
-            const uint16_t* base = first ? (x0 + c) : (x1 + (c - p.C0));
-            const long ld = first ? p.ld : p.ld1;
-            long r = row0 + rl;
-            for (; r + 7L * RPP < row_end; r += 8L * RPP) {      // 8 independent 16-B loads in flight per lane
-                u32x4_t v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const u32x4_t*>(base + (r + (long)k * RPP) * ld);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    float f[8];
-                    unpack8(v[k], f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float d = f[e] - pl[e]; s[e] += d; q[e] += d * d; }
-                }
-            }
-            for (; r + 3L * RPP < row_end; r += 4L * RPP) {
-                u32x4_t v[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const u32x4_t*>(base + (r + (long)k * RPP) * ld);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float f[8];
-                    unpack8(v[k], f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float d = f[e] - pl[e]; s[e] += d; q[e] += d * d; }
-                }
-            }
-            for (; r < row_end; r += RPP) {
-                const u32x4_t v = *reinterpret_cast<const u32x4_t*>(base + r * ld);
+        if (L.active) {
+            const GnSrc src = gn_src(p, cs * 8);
+            auto add = [&](const u32x4_t& v, long) {
                 float f[8];
                 unpack8(v, f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { const float d = f[e] - pl[e]; s[e] += d; q[e] += d * d; }
-            }
+            };
+            long r = row0 + rl;
+            gn_walk<8>(src.base, src.ld, r, row_end, RPP, add);      // 8 independent 16-B loads in flight per lane
+            gn_walk<4>(src.base, src.ld, r, row_end, RPP, add);
+            gn_walk<1>(src.base, src.ld, r, row_end, RPP, add);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { lsum[rl * C + cs * 8 + e] = s[e]; lsq[rl * C + cs * 8 + e] = q[e]; }
         }
@@ -112,9 +142,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const VmvGroupNormParams 
         if (p.totals) {        // two-limb fixed-point 64-bit atomics: order-independent, hence deterministic (vmv.h)
             // Atomics on one 64-B record serialise at ~20 ns each wherever they are resolved (measured: 256 chunks x 4 adds on
             // one record = +20 us on a 17-us pass, linear in the chunk count: tools/experiments/gn_bench.py), so a record is
-            // kept GN_NREP times and consecutive chunks take consecutive replicas; integer adds: the fold stays exact
+            // kept VMV_GN_NREP times and consecutive chunks take consecutive replicas; integer adds: the fold stays exact
             unsigned long long* rec = reinterpret_cast<unsigned long long*>(p.totals) +
-                                      (((long)stat * 32 + tid) * GN_NREP + (chunk & (GN_NREP - 1))) * GN_REC;
+                                      (((long)stat * 32 + tid) * VMV_GN_NREP + (chunk & (VMV_GN_NREP - 1))) * VMV_GN_REC;
             gn_add2(rec, 0, s);
             gn_add2(rec, 1, q);
             if (chunk == 0) rec[4] = (unsigned long long)__float_as_uint(pil[tid]);       // (replica 0 carries the pilot)
@@ -150,12 +180,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const VmvGroupNormParams 
         const int R = p.fold_ranks > 1 ? p.fold_ranks : 1;
         if (p.totals) {      // two-limb integer totals per (rank, stat, group), each relative to that rank's pilot: moved to rank 0's
                              // pilot and summed in fp64 (R shards of equal size: frame-parallel pixel shards)
-            static_assert(GN_NREP == 8, "one replica per sub-lane");
+            static_assert(VMV_GN_NREP == 8, "one replica per sub-lane");
             const double nr = (double)p.rows_per_stat * (double)cpg;
             double S = 0.0, Q = 0.0, P0 = 0.0;
             for (int r = 0; r < R; ++r) {
                 const long long* rec = reinterpret_cast<const long long*>(p.totals) +
-                                       ((((long)r * nstat + stat) * 32 + g) * GN_NREP + sub) * GN_REC;
+                                       ((((long)r * nstat + stat) * 32 + g) * VMV_GN_NREP + sub) * VMV_GN_REC;
                 long long l0 = rec[0], l1 = rec[1], l2 = rec[2], l3 = rec[3];
                 const long long pb = __shfl(rec[4], tid & 56, 64);         // replica 0's
 #pragma unroll
@@ -197,12 +227,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const VmvGroupNormParams 
     __syncthreads();
     if (p.totals_clear && blockIdx.x == 0 && blockIdx.y == 0)     // the NEXT norm's accumulators (never the ones read above)
         for (int i = tid; i < p.clear_count; i += 256) p.totals_clear[i] = 0;
-    for (int c = tid; c < C; c += 256) {
-        const int g = c / cpg;
-        const float sc = s_rstd[g] * p.gamma[c];
-        scale[c] = sc;
-        shift[c] = p.beta[c] - s_mean[g] * sc;
-    }
+    gn_scale_shift(scale, shift, s_mean, s_rstd, p, 0, C, cpg);
     __syncthreads();
     if (table) {
         for (int c = tid; c < C; c += 256) {
@@ -217,44 +242,21 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const VmvGroupNormParams 
     if (row_end > stat_end) row_end = stat_end;
     // thread -> fixed 16-byte column slot (its 8 scale/shift pairs live in registers), rows strided: no integer
     // division and no LDS traffic in the streaming loop, 4 independent loads in flight per lane.
-    const int TPR = CS < 256 ? CS : 256;
-    const int RPP = 256 / TPR;
-    const int rl = tid / TPR, cl = tid - rl * TPR;
-    const uint16_t* x0 = reinterpret_cast<const uint16_t*>(p.x);
-    const uint16_t* x1 = reinterpret_cast<const uint16_t*>(p.x1);
+    const GnLane L(CS);
     uint16_t* y = reinterpret_cast<uint16_t*>(p.y);
-    if (rl < RPP) {
-        for (int cs = cl; cs < CS; cs += TPR) {
+    if (L.active) {
+        for (int cs = L.cl; cs < CS; cs += L.TPR) {
             const int c = cs * 8;
-            float a[8], b[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { a[e] = scale[c + e]; b[e] = shift[c + e]; }
-            const bool first = c < p.C0;
-            const uint16_t* src = first ? (x0 + c) : (x1 + (c - p.C0));
-            const long ld = first ? p.ld : p.ld1;
+            const GnAffine af(scale + c, shift + c);
+            const GnSrc src = gn_src(p, c);
             uint16_t* dst = y + c;
             auto stream = [&](auto silu_tag) {
-                constexpr bool SILU = decltype(silu_tag)::value;
-                auto xform = [&](const u32x4_t& v) {
-                    float f[8];
-                    unpack8(v, f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        f[e] = f[e] * a[e] + b[e];
-                        if constexpr (SILU) f[e] = silu_f(f[e]);
-                    }
-                    return pack8(f);
+                auto put = [&](const u32x4_t& v, long row) {
+                    *reinterpret_cast<u32x4_t*>(dst + row * p.ldy) = af.apply<decltype(silu_tag)::value>(v);
                 };
-                long r = row0 + rl;
-                for (; r + 3L * RPP < row_end; r += 4L * RPP) {
-                    u32x4_t v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const u32x4_t*>(src + (r + (long)k * RPP) * ld);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4_t*>(dst + (r + (long)k * RPP) * p.ldy) = xform(v[k]);
-                }
-                for (; r < row_end; r += RPP)
-                    *reinterpret_cast<u32x4_t*>(dst + r * p.ldy) = xform(*reinterpret_cast<const u32x4_t*>(src + r * ld));
+                long r = row0 + L.rl;
+                gn_walk<4>(src.base, src.ld, r, row_end, L.RPP, put);
+                gn_walk<1>(src.base, src.ld, r, row_end, L.RPP, put);
             };
             if (p.silu) stream(std::true_type{}); else stream(std::false_type{});
         }
@@ -278,11 +280,10 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
     const int cpg = C >> 5;
     const int G = CW / cpg;                       // groups of this block
     const int SW = CW >> 3;                       // 16-byte slots per staged row
-    const int TPR = SW < 256 ? SW : 256;
-    const int RPP = 256 / TPR;
+    const GnLane L(SW);
+    const int TPR = L.TPR, RPP = L.RPP, rl = L.rl, cl = L.cl;
+    const bool active = L.active;
     const int tid = threadIdx.x;
-    const int rl = tid / TPR, cl = tid - rl * TPR;
-    const bool active = rl < RPP;
     const int stat = blockIdx.y, c0 = blockIdx.x * CW;
     const int rows = p.rows_per_stat;
     const long row0 = (long)stat * rows;
@@ -292,18 +293,15 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
     float* shift = scale + CW;                                        // [CW]
     float* s_mean = shift + CW;                                       // [32]
     float* s_rstd = s_mean + 32;                                      // [32]
-    const uint16_t* x0 = reinterpret_cast<const uint16_t*>(p.x);
-    const uint16_t* x1 = reinterpret_cast<const uint16_t*>(p.x1);
     // ---- pass 1: stream in, stage, column sums
     for (int cs = cl; cs < SW; cs += TPR) {
         float s[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) s[e] = 0.f;
         if (active) {
-            const int c = c0 + cs * 8;
-            const bool first = c < p.C0;
-            const uint16_t* base = first ? (x0 + c) : (x1 + (c - p.C0));
-            const long ld = first ? p.ld : p.ld1;
+            const GnSrc src = gn_src(p, c0 + cs * 8);
+            const uint16_t* base = src.base;
+            const long ld = src.ld;
             int r = rl;
             // GNF_UNR loads in flight per lane (more were tried: profiles/r5_gnf_unroll_ab.log)
             for (; r + (GNF_UNR - 1) * RPP < rows; r += GNF_UNR * RPP) {
@@ -372,33 +370,17 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const VmvGroupNormParams 
     }
     __syncthreads();
     group_totals(s_rstd, [&](float q) { return rsqrtf(q / n + p.eps); });
-    for (int c = tid; c < CW; c += 256) {
-        const int g = c / cpg;
-        const float sc = s_rstd[g] * p.gamma[c0 + c];
-        scale[c] = sc;
-        shift[c] = p.beta[c0 + c] - s_mean[g] * sc;
-    }
+    gn_scale_shift(scale, shift, s_mean, s_rstd, p, c0, CW, cpg);
     __syncthreads();
     // ---- apply from the stage
     uint16_t* y = reinterpret_cast<uint16_t*>(p.y);
     if (active) {
         for (int cs = cl; cs < SW; cs += TPR) {
-            float a[8], b[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { a[e] = scale[cs * 8 + e]; b[e] = shift[cs * 8 + e]; }
+            const GnAffine af(scale + cs * 8, shift + cs * 8);
             uint16_t* dst = y + c0 + cs * 8;
             auto run = [&](auto silu_tag) {
-                constexpr bool SILU = decltype(silu_tag)::value;
-                for (int r = rl; r < rows; r += RPP) {
-                    float f[8];
-                    unpack8(stage[(size_t)r * SW + cs], f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        f[e] = f[e] * a[e] + b[e];
-                        if constexpr (SILU) f[e] = silu_f(f[e]);
-                    }
-                    *reinterpret_cast<u32x4_t*>(dst + (row0 + r) * p.ldy) = pack8(f);
-                }
+                for (int r = rl; r < rows; r += RPP)
+                    *reinterpret_cast<u32x4_t*>(dst + (row0 + r) * p.ldy) = af.apply<decltype(silu_tag)::value>(stage[(size_t)r * SW + cs]);
             };
             if (p.silu) run(std::true_type{}); else run(std::false_type{});
         }
@@ -507,15 +489,43 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const VmvSoftmaxParam
     }
 }
 
-int gn_check(const VmvGroupNormParams& p) {
-    if (!p.x || (!p.partial && !p.totals)) return VMV_ENULL;
+// ws: the call reads or writes a statistics workspace (partial sums or totals, chunk_rows rows per block) — all but the fused form
+int gn_check(const VmvGroupNormParams& p, bool ws) {
+    if (!p.x || (ws && !p.partial && !p.totals)) return VMV_ENULL;
     const int C = p.C0 + p.C1;
     if (C <= 0 || (C & 31) || (p.C0 & 7) || (p.C1 & 7)) return VMV_EINVAL;
     if (p.C1 > 0 && !p.x1) return VMV_ENULL;
-    if (p.rows <= 0 || p.rows_per_stat <= 0 || (p.rows % p.rows_per_stat) || p.chunk_rows <= 0) return VMV_EINVAL;
+    if (p.rows <= 0 || p.rows_per_stat <= 0 || (p.rows % p.rows_per_stat) || (ws && p.chunk_rows <= 0)) return VMV_EINVAL;
     if (!vmv_aligned16(p.x) || (p.ld & 7) || (p.C1 > 0 && (!vmv_aligned16(p.x1) || (p.ld1 & 7)))) return VMV_EALIGN;
     if (C > 4096) return VMV_ERANGE;
     return VMV_OK;
+}
+// the output side: y (table: the fp32 scale / shift table, no row pitch), gamma, beta
+int gn_check_out(const VmvGroupNormParams& p, bool table) {
+    if (!p.y || !p.gamma || !p.beta) return VMV_ENULL;
+    if (table && p.silu) return VMV_EINVAL;                // an activation cannot ride in an affine table
+    if (!vmv_aligned16(p.y) || (!table && (p.ldy & 7)) || !vmv_aligned16(p.gamma) || !vmv_aligned16(p.beta)) return VMV_EALIGN;
+    return VMV_OK;
+}
+struct GnGrid { int nstat, nchunk; };
+GnGrid gn_grid(const VmvGroupNormParams& p) { return {p.rows / p.rows_per_stat, (p.rows_per_stat + p.chunk_rows - 1) / p.chunk_rows}; }
+
+// vmv_groupnorm_apply (grid = (row blocks, nstat)) and vmv_groupnorm_table (grid = (1, nstat), the table in p.y)
+int gn_apply_launch(const VmvGroupNormParams* pp, void* stream, bool table) {
+    if (!pp) return VMV_ENULL;
+    const VmvGroupNormParams& p = *pp;
+    if (const int rc = gn_check(p, true)) return rc;
+    if (const int rc = gn_check_out(p, table)) return rc;
+    if (p.fold_ranks > 1 && !p.totals) return VMV_EINVAL;      // shards are folded through the totals records (they carry the pilots)
+    const int C = p.C0 + p.C1;
+    const GnGrid g = gn_grid(p);
+    // ~64 KB of input per block: >= 1k blocks in flight at the large levels, table set-up amortised
+    int apply_rows = (65536 / (C * 2));
+    if (apply_rows < 1 || table) apply_rows = 1;
+    const int nblk = table ? 1 : (p.rows_per_stat + apply_rows - 1) / apply_rows;
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, g.nstat), dim3(256), (size_t)(2 * C + 64) * sizeof(float),
+                       reinterpret_cast<hipStream_t>(stream), p, g.nchunk, apply_rows, g.nstat, table ? reinterpret_cast<float*>(p.y) : nullptr);
+    return vmv_launch_status();
 }
 
 }  // namespace
@@ -523,77 +533,32 @@ int gn_check(const VmvGroupNormParams& p) {
 extern "C" int vmv_groupnorm_stats(const VmvGroupNormParams* pp, void* stream) {
     if (!pp) return VMV_ENULL;
     const VmvGroupNormParams& p = *pp;
-    int rc = gn_check(p);
-    if (rc != VMV_OK) return rc;
+    if (const int rc = gn_check(p, true)) return rc;
     const int C = p.C0 + p.C1;
-    const int CS = C >> 3;
-    const int TPR = CS < 256 ? CS : 256;
-    const int RPP = 256 / TPR;
-    const int nstat = p.rows / p.rows_per_stat;
-    const int nchunk = (p.rows_per_stat + p.chunk_rows - 1) / p.chunk_rows;
-    const size_t shbytes = ((size_t)2 * RPP * C + 32) * sizeof(float);
+    const GnGrid g = gn_grid(p);
+    const size_t shbytes = ((size_t)2 * GnSlots(C >> 3).RPP * C + 32) * sizeof(float);
     if (p.totals && (((uintptr_t)p.totals) & 7)) return VMV_EALIGN;
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, nstat), dim3(256), shbytes, reinterpret_cast<hipStream_t>(stream), p, nchunk);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(g.nchunk, g.nstat), dim3(256), shbytes, reinterpret_cast<hipStream_t>(stream), p, g.nchunk);
     return vmv_launch_status();
 }
 
-extern "C" int vmv_groupnorm_apply(const VmvGroupNormParams* pp, void* stream) {
-    if (!pp) return VMV_ENULL;
-    const VmvGroupNormParams& p = *pp;
-    int rc = gn_check(p);
-    if (rc != VMV_OK) return rc;
-    if (!p.y || !p.gamma || !p.beta) return VMV_ENULL;
-    if (!vmv_aligned16(p.y) || (p.ldy & 7) || !vmv_aligned16(p.gamma) || !vmv_aligned16(p.beta)) return VMV_EALIGN;
-    if (p.fold_ranks > 1 && !p.totals) return VMV_EINVAL;      // shards are folded through the totals records (they carry the pilots)
-    const int C = p.C0 + p.C1;
-    const int nstat = p.rows / p.rows_per_stat;
-    const int nchunk = (p.rows_per_stat + p.chunk_rows - 1) / p.chunk_rows;
-    // ~64 KB of input per block: >= 1k blocks in flight at the large levels, table set-up amortised
-    int apply_rows = (65536 / (C * 2));
-    if (apply_rows < 1) apply_rows = 1;
-    const int nblk = (p.rows_per_stat + apply_rows - 1) / apply_rows;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, nstat), dim3(256), (size_t)(2 * C + 64) * sizeof(float),
-                       reinterpret_cast<hipStream_t>(stream), p, nchunk, apply_rows, nstat, nullptr);
-    return vmv_launch_status();
-}
-
-extern "C" int vmv_groupnorm_table(const VmvGroupNormParams* pp, void* stream) {
-    if (!pp) return VMV_ENULL;
-    const VmvGroupNormParams& p = *pp;
-    int rc = gn_check(p);
-    if (rc != VMV_OK) return rc;
-    if (!p.y || !p.gamma || !p.beta) return VMV_ENULL;
-    if (p.silu) return VMV_EINVAL;                         // an activation cannot ride in an affine table
-    if ((((uintptr_t)p.y) & 15) || !vmv_aligned16(p.gamma) || !vmv_aligned16(p.beta)) return VMV_EALIGN;
-    if (p.fold_ranks > 1 && !p.totals) return VMV_EINVAL;
-    const int C = p.C0 + p.C1;
-    const int nstat = p.rows / p.rows_per_stat;
-    const int nchunk = (p.rows_per_stat + p.chunk_rows - 1) / p.chunk_rows;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(1, nstat), dim3(256), (size_t)(2 * C + 64) * sizeof(float),
-                       reinterpret_cast<hipStream_t>(stream), p, nchunk, 1, nstat, reinterpret_cast<float*>(p.y));
-    return vmv_launch_status();
-}
+extern "C" int vmv_groupnorm_apply(const VmvGroupNormParams* pp, void* stream) { return gn_apply_launch(pp, stream, false); }
+extern "C" int vmv_groupnorm_table(const VmvGroupNormParams* pp, void* stream) { return gn_apply_launch(pp, stream, true); }
 
 extern "C" int vmv_groupnorm_fused(const VmvGroupNormParams* pp, int32_t cols, void* stream) {
     if (!pp) return VMV_ENULL;
-    VmvGroupNormParams p = *pp;
-    if (!p.partial) p.partial = reinterpret_cast<float*>(const_cast<void*>(p.x));      // (unused here; gn_check wants it non-NULL)
-    if (p.chunk_rows <= 0) p.chunk_rows = 1;
-    int rc = gn_check(p);
-    if (rc != VMV_OK) return rc;
-    if (!p.y || !p.gamma || !p.beta) return VMV_ENULL;
-    if (!vmv_aligned16(p.y) || (p.ldy & 7) || !vmv_aligned16(p.gamma) || !vmv_aligned16(p.beta)) return VMV_EALIGN;
+    const VmvGroupNormParams& p = *pp;
+    if (const int rc = gn_check(p, false)) return rc;
+    if (const int rc = gn_check_out(p, false)) return rc;
     const int C = p.C0 + p.C1, cpg = C >> 5;
     if (cols <= 0 || (cols & 7) || (cols % cpg) || (C % cols)) return VMV_EINVAL;
     if (cols > 256) return VMV_ERANGE;              // the column fold is one thread per column of a 256-thread block
     if (p.fold_ranks > 1) return VMV_EINVAL;
     if ((long)p.rows_per_stat * cols * 2 > VMV_GN_FUSED_BYTES) return VMV_ERANGE;
-    const int SW = cols >> 3;
-    const int TPR = SW < 256 ? SW : 256, RPP = 256 / TPR;
-    const size_t shbytes = (size_t)p.rows_per_stat * cols * 2 + (size_t)(RPP * cols + 2 * cols + 64) * sizeof(float);
+    const size_t shbytes = (size_t)p.rows_per_stat * cols * 2 + (size_t)(GnSlots(cols >> 3).RPP * cols + 2 * cols + 64) * sizeof(float);
+    if (shbytes > 160 * 1024) return VMV_ERANGE;
     static std::atomic<unsigned long long> attr{0};
     if (const int rc_attr = vmv_lds_attr_once(attr, reinterpret_cast<const void*>(&gn_fused_kernel), 160 * 1024)) return rc_attr;
-    if (shbytes > 160 * 1024) return VMV_ERANGE;
     hipLaunchKernelGGL(gn_fused_kernel, dim3(C / cols, p.rows / p.rows_per_stat), dim3(256), shbytes,
                        reinterpret_cast<hipStream_t>(stream), p, cols);
     return vmv_launch_status();

@@ -424,7 +424,8 @@ class Stream:
         self._go(L.OP_GEMM, params, self.lib.vmv_gemm, label)
 
     def groupnorm(self, params, label="gn"):
-        """statistics + apply; one fused launch when the stat group fits on chip (gn_fused_cols), else two."""
+        """statistics + apply; one fused launch when the stat group fits on chip (gn_fused_cols), else two.  For direct callers (tests,
+        tools): the engines' plans pick their launches in PlanBuilder._gn."""
         cols = 0 if (params.totals or params.fold_ranks > 1) else gn_fused_cols(params.rows_per_stat, params.C0 + params.C1)
         if cols:
             return self.groupnorm_fused(params, cols, label)

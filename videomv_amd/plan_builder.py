@@ -1,6 +1,6 @@
 """What every engine (UNet, LGM, VAE, CLIP towers) needs to record a plan of C-ABI launches: pooled activation buffers, the recording
 stream with its tile-table hook, one split-K slab, and the launch forms the networks share — the implicit GEMM on packed weights, the
-per-frame GroupNorm, the ResNet block, the stride-2 and nearest-x2 convolutions."""
+GroupNorm, the ResNet block, the stride-2 and nearest-x2 convolutions."""
 from typing import Dict, List
 
 import torch
@@ -102,17 +102,51 @@ class PlanBuilder:
         (stream or self.S).gemm(ops.gemm_params(M, N, segs, Wt, out.ptr if isinstance(out, Act) else out,
                                                 ldo if ldo is not None else out.C, bias=bias, **kw), label)
 
-    def _gn(self, label, srcs, rows_per_stat, key, eps, silu) -> Act:
-        """GroupNorm(32) (+ SiLU) of the channel concat of one or two sources, statistics per `rows_per_stat` rows (one frame): one
-        fused launch when the stat group fits on chip, else statistics + apply (ops.Stream.groupnorm)."""
+    comm = None         # frame-parallel communicator (UNetEngine)
+
+    def _gn(self, label, srcs, rows_per_stat, key, eps, silu, table: Act = None, all_frames=False) -> Act:
+        """Every GroupNorm(32) (+ SiLU) of every engine: the channel concat of one or two sources, statistics per `rows_per_stat` rows,
+        into a new Act — or, table given (fp32 [nstat * 2][C]), its scale / shift table for a GEMM that folds the apply pass
+        (gemm_params(gn_table=...)).  The launches:
+          fused          one launch where the stat group fits on chip (ops.gn_fused_cols); never to a table, never frame-parallel
+          stats + second on the per-chunk partial sums: rows_per_stat = one frame.  second = apply | table
+          stats + second on integer totals (all_frames: statistics over every frame; the UNet, _gn_totals): up to 256 chunks
+                         per stat group, which the statistics pass folds itself.  Frame-parallel: the input is the pixel-major shard, so
+                         each rank sums its HW/R pixels of all frames, the totals are all-gathered in between and every rank folds all
+                         R shards in the same order (bitwise identical statistics)."""
         rows, C0 = srcs[0].rows, srcs[0].C
         C1 = srcs[1].C if len(srcs) > 1 else 0
-        y = self.act(rows, C0 + C1)
+        nstat = rows // rows_per_stat
+        y = table or self.act(rows, C0 + C1)
         assert ops.gn_partial_floats(rows, rows_per_stat, C0 + C1) <= self._gnws.numel()
-        self.S.groupnorm(ops.gn_params(srcs[0].ptr, C0, C0, rows, rows_per_stat, self._gnws, self.wt[key + ".weight"],
-                                       self.wt[key + ".bias"], eps, silu, y.ptr, C0 + C1,
-                                       x1=srcs[1].ptr if C1 else None, ld1=C1, C1=C1), label)
+        params = lambda **kw: ops.gn_params(srcs[0].ptr, C0, C0, rows, rows_per_stat, self._gnws, self.wt[key + ".weight"],
+                                            self.wt[key + ".bias"], eps, silu, y.ptr, C0 + C1,
+                                            x1=srcs[1].ptr if C1 else None, ld1=C1, C1=C1, **kw)
+        second = self.S.groupnorm_table if table else self.S.groupnorm_apply
+        fused = 0 if table or (all_frames and self.comm is not None) else ops.gn_fused_cols(rows_per_stat, C0 + C1)
+        if fused:
+            self.S.groupnorm_fused(params(), fused, label)
+        elif not all_frames:
+            gnp = params()
+            self.S.groupnorm_stats(gnp, label)
+            second(gnp, label)
+        else:
+            tot, nxt, gather = self._gn_totals(nstat)
+            clr = dict(totals_clear=nxt, clear_count=nstat * ops.GN_TOT)      # (second clears the NEXT norm's accumulators)
+            if gather is None:
+                gnp = params(totals=tot, **clr)
+                self.S.groupnorm_stats(gnp, label)
+                second(gnp, label)
+            else:
+                self.S.groupnorm_stats(params(totals=tot), label)
+                second(params(totals=gather(label + ".totals.gather"), fold_ranks=self.R, **clr), label)
         return y
+
+    def _gn_totals(self, nstat):
+        """The integer-totals accumulators of the next all-frame norm (nstat stat groups) -> (its own: zero when its statistics pass
+        starts, the ones its second launch clears, gather).  gather: None, or on a frame-parallel plan f(label) that records the
+        all-gather of the ranks' totals -> the gathered [R] records."""
+        raise NotImplementedError(f"{type(self).__name__} records no all-frame GroupNorm")
 
     def _conv_res(self, p, srcs, h, w, eps, skip, keys=("norm1", "norm1", "conv1", "norm2", "norm2"), conv1_kw=None, res_scale=0.0) -> Act:
         """ResNet block: GroupNorm + SiLU -> conv3x3 -> GroupNorm + SiLU -> conv3x3 + shortcut.  srcs = [x] or [x, skip] (channel

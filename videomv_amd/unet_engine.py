@@ -400,42 +400,20 @@ class UNetEngine(PlanBuilder):
         self.S.gemm(gp, p)
         return y, 2 * h, 2 * w
 
-    def _gn(self, label, srcs, rows_per_stat, wkey, eps, silu, all_frames=False) -> Act:
-        """all_frames: a 5-D norm whose statistics span every frame.  Frame-parallel: the input is the
-        pixel-major shard, so each rank sums its HW/R pixels of all frames, the per-chunk partial sums are
-        all-gathered, and every rank folds all R shards in the same order (bitwise identical statistics)."""
-        if not all_frames:      # (one fused launch when the stat group fits on chip — the small levels — else stats + apply)
-            return super()._gn(label, srcs, rows_per_stat, wkey, eps, silu)
-        x, rows, Cc = srcs[0], srcs[0].rows, srcs[0].C
-        y = self.act(rows, Cc)
-        assert ops.gn_partial_floats(rows, rows_per_stat, Cc) <= self._gnws.numel()
-        params = lambda **kw: ops.gn_params(x.ptr, Cc, Cc, rows, rows_per_stat, self._gnws, self.w[wkey + ".weight"], self.w[wkey + ".bias"],
-                                            eps, silu, y.ptr, Cc, **kw)
-        fused = 0 if self.comm is not None else ops.gn_fused_cols(rows_per_stat, Cc)
-        if fused:               # all-frame norm whose stat group still fits on chip (L3 / middle block)
-            self.S.groupnorm_fused(params(), fused, label)
-        else:                   # up to 256 chunks per stat group -> a one-block fold after the stats folds them once (pre-folded totals)
-            self._gn_all_frames(label, rows // rows_per_stat, params, self.S.groupnorm_apply)
-        return y
-
-    def _gn_all_frames(self, label, nstat, params, second):
-        """The two launches of a norm whose statistics span all frames: the statistics pass adds into the integer totals of one of the
-        two accumulator buffers (a ticket: consecutive norms alternate), `second` (S.groupnorm_apply | S.groupnorm_table) folds them and
-        clears the OTHER buffer for the next norm.  params(**totals arguments) -> the norm's gn_params.  Frame-parallel plans all-gather
-        the ranks' totals in between and fold all R shards."""
+    def _gn_totals(self, nstat):
+        """PlanBuilder._gn's accumulators of an all-frame norm: two buffers, a ticket — consecutive norms alternate, each clears the
+        other's for the next one.  (Every all-frame norm of an engine has nstat = B.)"""
         assert nstat <= self.B_ctx
         tot, nxt = self._gn_tot2[self._gn_tot_k & 1], self._gn_tot2[(self._gn_tot_k + 1) & 1]
         self._gn_tot_k += 1
-        clr = dict(totals_clear=nxt, clear_count=nstat * ops.GN_TOT)      # (every all-frame norm of an engine has nstat = B)
         if self.comm is None:
-            gnp = params(totals=tot, **clr)
-            self.S.groupnorm_stats(gnp, label)
-            second(gnp, label)
-            return
-        self.S.groupnorm_stats(params(totals=tot), label)
-        loc, allr = tot[: nstat * ops.GN_TOT], self._gn_tot_all[: nstat * ops.GN_TOT * self.R]
-        self._collective(L.COMM_ALL_GATHER, allr, loc, label + ".totals.gather")
-        second(params(totals=self._gn_tot_all, fold_ranks=self.R, **clr), label)
+            return tot, nxt, None
+
+        def gather(label):
+            loc, allr = tot[: nstat * ops.GN_TOT], self._gn_tot_all[: nstat * ops.GN_TOT * self.R]
+            self._collective(L.COMM_ALL_GATHER, allr, loc, label)
+            return self._gn_tot_all
+        return tot, nxt, gather
 
     def _gn_folded_proj_in(self, p, x: Act, T, rps, out: Act, all_frames) -> bool:
         """SpatialTransformer / TemporalTransformer head (util.py:354-360, 1043-1050): GroupNorm -> proj_in with the norm's apply
@@ -454,16 +432,7 @@ class UNetEngine(PlanBuilder):
         if not self.S.lib.vmv_gemm_rs_ok(C.byref(gp)):
             self.release(tab)
             return False
-        label = p + ".norm"
-        params = lambda **kw: ops.gn_params(x.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{p}.norm.weight"], self.w[f"{p}.norm.bias"], 1e-6, False,
-                                            tab.ptr, Cc, **kw)
-        assert ops.gn_partial_floats(T, rps, Cc) <= self._gnws.numel()
-        if all_frames:          # long stat groups: integer totals (as _gn)
-            self._gn_all_frames(label, nstat, params, self.S.groupnorm_table)
-        else:
-            gnp = params()
-            self.S.groupnorm_stats(gnp, label)
-            self.S.groupnorm_table(gnp, label)
+        self._gn(p + ".norm", [x], rps, f"{p}.norm", 1e-6, False, table=tab, all_frames=all_frames)
         self.S.gemm(gp, p + ".proj_in")
         self.release(tab)
         return True
@@ -492,10 +461,7 @@ class UNetEngine(PlanBuilder):
         if not (trs or self.S.lib.vmv_gemm_tfr_ok(C.byref(gp))):
             self.release(tab)
             return False
-        assert ops.gn_partial_floats(T, rps, Cc) <= self._gnws.numel()
-        params = lambda **kw: ops.gn_params(cur.ptr, Cc, Cc, T, rps, self._gnws, self.w[f"{q}.0.weight"], self.w[f"{q}.0.bias"], 1e-5, False,
-                                            tab.ptr, Cc, **kw)
-        self._gn_all_frames(q + ".gn", nstat, params, self.S.groupnorm_table)
+        self._gn(q + ".gn", [cur], rps, f"{q}.0", 1e-5, False, table=tab, all_frames=True)
         self.S.gemm(gp, q)
         self.release(tab)
         return True
