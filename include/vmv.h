@@ -723,6 +723,57 @@ typedef struct {
 } VmvGsMeshComponentsParams;
 int vmv_gs_mesh_components(const VmvGsMeshComponentsParams* p, void* stream);   /* vmv_sizeof(110) */
 
+/* Texture baking: the colours of the depth-mapped views blended over a triangle mesh into a texture atlas (csrc/gs_mesh_bake.hip;
+ * videomv_amd/gs_mesh.py: texture_atlas, bake_texture, save_mesh_obj).  Additive: the ABI version does not change, callers detect the
+ * entry by its symbol.
+ * THE ATLAS (closed form): P = patch >= 4, cells = ceil(n_faces / 2), Wc = ceil(sqrt(cells)), T = tex_size = P Wc.  Cell k is the P x P
+ * square at column k % Wc, row k / Wc (rows top-down); its texel (i, j) (column i, row j) has its centre at (i + 0.5, j + 0.5).  Face 2k
+ * owns the texels with i + j <= P - 1 and sees them at (s, t) = (i + 0.5, j + 0.5); face 2k + 1 owns i + j >= P and sees them flipped,
+ * (s, t) = (P - i - 0.5, P - j - 0.5).  In its own frame a face's UV triangle is a = (0.5, 0.5), b = (P - 2.5, 0.5), c = (0.5, P - 2.5) for
+ * its corners 0, 1, 2: a bilinear lookup anywhere inside it touches only texels the face owns; the owned texels outside it are padding.
+ * A texel whose face index is >= n_faces belongs to no face.
+ * One thread owns one texel and walks the views in index order: plain loads and stores, no atomics, two calls give the same bits.
+ * For an owned texel of face (i0, i1, i2) with vertices v0, v1, v2 and vertex colours c0, c1, c2:
+ *   beta = clamp((s - 0.5) / (P - 3), 0, 1), gamma likewise from t; if beta + gamma > 1 both are divided by their sum;
+ *   alpha = 1 - beta - gamma (padding takes the nearest point of the triangle);  p = alpha v0 + beta v1 + gamma v2;
+ *   n = (v1 - v0) x (v2 - v0) / its length; a zero cross product: no view contributes.  Then, for each view v, in this order:
+ *   1. (xv, yv, z, _) = [p, 1] @ views[v]; z <= z_min: the view is skipped
+ *   2. px = ((xv / (z tan_half_fov) + 1) size - 1) / 2, likewise py (vmv_gs_tsdf_integrate's arithmetic); skipped unless
+ *      0 <= px <= size - 1 and 0 <= py <= size - 1 (tested on the floats)
+ *   3. cos = -(n_c . p_c) / |p_c| with p_c = (xv, yv, z), n_c = n @ views[v][:3, :3]; cos <= cos_min: skipped (back-facing or grazing)
+ *   4. d = depth[v][floor(py + 0.5)][floor(px + 0.5)]; d == 0 or |d - z| > depth_tol: skipped (no surface there, or another one)
+ *   5. w = cos^2, c = the bilinear sample of colour[v] at (px, py) (taps floor(px), min(floor(px) + 1, size - 1), likewise y);
+ *      sum += w c, W += w
+ * out: four fp32 planes [T][T] at out + k * plane_stride: R, G, B, W.  W > 0: RGB = sum / W.  W == 0 (no view contributed): RGB =
+ * alpha c0 + beta c1 + gamma c2.  A texel of no face: RGB = 0.5, W = -1.
+ * A face with any index outside [0, n_vertices) is treated as no face and sets bit 0 of *status (the range test comes before any access
+ * that uses the index); the call clears *status itself, on ``stream``.
+ * Argument checks run before any launch and need no device: VMV_ENULL (p or any pointer null), VMV_EINVAL (n_faces < 1, n_vertices < 1,
+ * face_stride < 3, n_views < 1, size < 1, tan_half_fov / z_min / depth_tol not positive, cos_min outside [0, 1), patch < 4, tex_size
+ * != P Wc, plane_stride < T^2), VMV_ERANGE (T > 8192, size > 32768, n_faces or n_vertices beyond int32), VMV_EALIGN (faces not 8-byte
+ * aligned, another pointer not 4-byte aligned).  No allocation, no synchronisation. */
+typedef struct {
+    const float*   verts;        /* [n_vertices][3] world positions                                                            */
+    const float*   vert_colours; /* [n_vertices][3] in [0,1]: the fallback where no view sees a texel                          */
+    const int64_t* faces;        /* [n_faces] triples of vertex indices, face f at faces + f * face_stride                     */
+    int64_t  face_stride;        /* elements from one face to the next, >= 3                                                   */
+    int64_t  n_faces;            /* >= 1                                                                                       */
+    int64_t  n_vertices;         /* >= 1                                                                                       */
+    const float* depth;          /* [n_views][size][size] view depth z per pixel, 0 = no surface (as VmvGsTsdfParams.depth)    */
+    const float* colour;         /* [n_views][3][size][size] in [0,1]                                                          */
+    const float* views;          /* [n_views][16] cam_view, row-vector convention                                              */
+    int32_t  n_views, size;
+    float    tan_half_fov;
+    float    z_min, depth_tol;   /* > 0                                                                                        */
+    float    cos_min;            /* in [0, 1)                                                                                  */
+    int32_t  patch;              /* P >= 4                                                                                     */
+    int32_t  tex_size;           /* T = P * ceil(sqrt(ceil(n_faces / 2))), <= 8192                                             */
+    float*   out;                /* 4 planes [T][T], plane k at out + k * plane_stride: R, G, B, W                             */
+    int64_t  plane_stride;       /* >= T^2 (floats)                                                                            */
+    int32_t* status;             /* out [1]: bit 0 a face index out of range                                                   */
+} VmvGsMeshBakeParams;
+int vmv_gs_mesh_bake(const VmvGsMeshBakeParams* p, void* stream);   /* vmv_sizeof(111) */
+
 /* ------------------------------------------------------------------------------------------------------
  * Block permute-copy (frame-sharded sampling, DESIGN.md §8: packs / unpacks the all-to-all buffers that switch an
  * activation between the frame-major shard [B][F/R][HW][C] and the pixel-major shard [B][F][HW/R][C]; the reference has

@@ -11,7 +11,13 @@ second.  Prints one JSON line per shape; --log FILE appends them to FILE.
 eager propagation that is gs_mesh.mesh_components' CPU fallback run on the device in the same process (the yardstick; it states the
 alternative), and of gs_mesh.drop_small_components (labelling, status read-back, masks and the remap).  Appends to
 profiles/gs_mesh_cc_bench.log unless --log names another file.
-    python tools/gs_mesh_bench.py --components [--shapes ...] [--iters 30] [--warmup 5]"""
+    python tools/gs_mesh_bench.py --components [--shapes ...] [--iters 30] [--warmup 5]
+--bake measures the texture baking instead (csrc/gs_mesh_bake.hip), on the meshes extracted at those shapes, baked from the V views they
+were fused from at patch 8 (or the largest patch below it whose atlas fits a texture of 8192) with a depth tolerance of 2 voxels: the median ms of one vmv_gs_mesh_bake call into preallocated planes, and of
+the torch restatement that is gs_mesh.bake_texture's CPU fallback run on the device in the same process (the yardstick; it states the
+alternative).  Rates: texel-view evaluations (texels of faces x V) per second and the plane bytes written (4 planes x T^2 x 4 B) per second.
+Appends to profiles/gs_mesh_bake_bench.log unless --log names another file.
+    python tools/gs_mesh_bench.py --bake [--shapes ...] [--patch 8] [--iters 30] [--warmup 5]"""
 import argparse
 import ctypes as C
 import json
@@ -80,6 +86,44 @@ def components_record(name, verts, cols, faces, iters, warmup):
                 dropped=res["d"][3])
 
 
+def bake_record(name, verts, cols, faces, depth, colour, views, tan, voxel, patch, iters, warmup):
+    """-> the JSON record of one mesh: the kernel and the torch restatement, and how far apart their textures are"""
+    from videomv_amd import _lib as L
+    from videomv_amd.gs_mesh import _bake_eager, texture_atlas
+    from videomv_amd.ops import _stream_ptr
+    n, m, V, S = int(verts.shape[0]), int(faces.shape[0]), int(depth.shape[0]), int(depth.shape[-1])
+    asked = patch
+    while patch > 4 and patch * (math.isqrt((m + 1) // 2 - 1) + 1) > 8192:      # the largest patch whose atlas fits a texture of 8192
+        patch -= 1
+    T, _ = texture_atlas(m, patch)
+    verts, cols, faces = verts.contiguous(), cols.contiguous(), faces.contiguous()
+    tex = torch.empty(4, T, T, dtype=torch.float32, device="cuda")
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    tol = 2.0 * voxel
+    p = L.GsMeshBakeParams()
+    p.verts, p.vert_colours, p.faces, p.face_stride, p.n_faces, p.n_vertices = verts.data_ptr(), cols.data_ptr(), faces.data_ptr(), 3, m, n
+    p.depth, p.colour, p.views, p.n_views, p.size, p.tan_half_fov = depth.data_ptr(), colour.data_ptr(), views.data_ptr(), V, S, tan
+    p.z_min, p.depth_tol, p.cos_min, p.patch, p.tex_size = 0.05, tol, 0.1, patch, T
+    p.out, p.plane_stride, p.status = tex.data_ptr(), T * T, status.data_ptr()
+    lib, stream = L.load(), _stream_ptr()
+    hip = median_ms(lambda: L.check(lib.vmv_gs_mesh_bake(C.byref(p), stream), "gs_mesh_bake"), iters, warmup)
+    res = {}
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
+    eager = median_ms(lambda: res.update(e=_bake_eager(verts, cols, faces, depth, colour, views.reshape(V, 4, 4), f32(tan), patch, T, f32(tol), f32(0.1),
+                                                       f32(0.05))), max(3, iters // 3), 1)
+    ref = res["e"][0]
+    owned = int((tex[3] >= 0).sum())
+    r3 = lambda t: [round(x, 4) for x in t]
+    diff = (tex[:3] - ref[:3]).abs().amax(0)[(tex[3] > 0) & (ref[3] > 0)]
+    return dict(mesh=name, vertices=n, faces=m, views=V, size=S, patch=patch, patch_asked=asked, texture=T, texels_of_faces=owned,
+                baked=round(int((tex[3] > 0).sum()) / max(owned, 1), 4), status=int(status), bake_ms=r3(hip), eager_ms=r3(eager),
+                ms_are="median, min, max", eager_over_hip=round(eager[0] / hip[0], 2),
+                texel_views_per_s=round(owned * V / (hip[0] * 1e-3), 0), plane_bytes_per_s=round(16.0 * T * T / (hip[0] * 1e-3), 0),
+                map_bytes=int(depth.numel() * 4 + colour.numel() * 4),
+                sets_that_differ_from_eager=round(float(((tex[3] > 0) != (ref[3] > 0)).float().mean()), 6),
+                baked_rgb_beyond_1e4_of_eager=round(float((diff > 1e-4).float().mean()), 6), baked_rgb_median_diff_vs_eager=float(diff.median()))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="128:24:256,256:48:512", help="R:V:S, comma-separated")
@@ -88,9 +132,12 @@ def main(argv=None):
     ap.add_argument("--gaussians", type=int, default=65536)
     ap.add_argument("--log", default=None)
     ap.add_argument("--components", action="store_true", help="measure the component labelling on the extracted meshes instead")
+    ap.add_argument("--bake", action="store_true", help="measure the texture baking on the extracted meshes instead")
+    ap.add_argument("--patch", type=int, default=8, help="--bake: texels per side of an atlas cell")
     args = ap.parse_args(argv)
-    if args.components and not args.log:
-        args.log = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gs_mesh_cc_bench.log")
+    if (args.components or args.bake) and not args.log:
+        args.log = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "gs_mesh_cc_bench.log" if args.components else "gs_mesh_bake_bench.log")
 
     def emit(rec):
         line = json.dumps(rec)
@@ -114,6 +161,12 @@ def main(argv=None):
             vol = TsdfVolume(R, half)
             vol.integrate(depth, views, r.tan_half_fov, colour=colour)
             emit(components_record(f"extract R={R} V={V} S={S}", *vol.extract(), args.iters, args.warmup))
+            continue
+        if args.bake:
+            vol = TsdfVolume(R, half)
+            vol.integrate(depth, views, r.tan_half_fov, colour=colour)
+            emit(bake_record(f"extract R={R} V={V} S={S}", *vol.extract(), depth, colour, views.reshape(V, 16).contiguous(), r.tan_half_fov, vol.voxel,
+                             args.patch, args.iters, args.warmup))
             continue
         vol = TsdfVolume(R, half)
         hip = median_ms(lambda: vol.integrate(depth, views, r.tan_half_fov, colour=colour), args.iters, args.warmup)

@@ -151,6 +151,14 @@ class GsMeshComponentsParams(C.Structure):
                 ("label", C.c_void_p), ("face_count", C.c_void_p), ("status", C.c_void_p)]
 
 
+class GsMeshBakeParams(C.Structure):
+    _fields_ = [("verts", C.c_void_p), ("vert_colours", C.c_void_p), ("faces", C.c_void_p), ("face_stride", C.c_int64),
+                ("n_faces", C.c_int64), ("n_vertices", C.c_int64), ("depth", C.c_void_p), ("colour", C.c_void_p), ("views", C.c_void_p),
+                ("n_views", C.c_int32), ("size", C.c_int32), ("tan_half_fov", C.c_float), ("z_min", C.c_float), ("depth_tol", C.c_float),
+                ("cos_min", C.c_float), ("patch", C.c_int32), ("tex_size", C.c_int32), ("out", C.c_void_p), ("plane_stride", C.c_int64),
+                ("status", C.c_void_p)]
+
+
 class CopyParams(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("inner16", C.c_int32), ("ss0", C.c_int64), ("ss1", C.c_int64), ("ss2", C.c_int64)]
@@ -245,6 +253,7 @@ SYMBOLS = {
     "vmv_gs_ssim_loss": (C.c_int, [C.POINTER(GsSsimLossParams), _P]),
     "vmv_gs_tsdf_integrate": (C.c_int, [C.POINTER(GsTsdfParams), _P]),
     "vmv_gs_mesh_components": (C.c_int, [C.POINTER(GsMeshComponentsParams), _P]),
+    "vmv_gs_mesh_bake": (C.c_int, [C.POINTER(GsMeshBakeParams), _P]),
     "vmv_latent_to_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_latent_to_rows_keep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "vmv_i2v_temporal_adapter": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
@@ -299,7 +308,7 @@ def load():
     if lib.vmv_elem_type() != (ELEM_F16 if _elem == "f16" else ELEM_BF16):
         raise RuntimeError(f"{LIB_PATH} was built for another element type")
     for which, st in ((OP_GEMM, GemmParams), (OP_GN_STATS, GroupNormParams), (OP_LAYERNORM, LayerNormParams),
-                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (108, GsDepthParams), (109, GsTsdfParams), (110, GsMeshComponentsParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
+                      (OP_ATTENTION, AttnParams), (OP_SOFTMAX, SoftmaxParams), (OP_COPY, CopyParams), (OP_FF, FfParams), (OP_COMM, CommParams), (103, GsParams), (104, GsBatchParams), (105, GsBackwardParams), (106, GsAdamParams), (107, GsSsimLossParams), (108, GsDepthParams), (109, GsTsdfParams), (110, GsMeshComponentsParams), (111, GsMeshBakeParams), (100, DdimParams), (101, GemmSeg), (102, SeqMap)):
         if lib.vmv_sizeof(which) != C.sizeof(st):
             raise RuntimeError(f"struct layout drift for {st.__name__}: C {lib.vmv_sizeof(which)} vs ctypes "
                                f"{C.sizeof(st)}")

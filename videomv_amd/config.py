@@ -82,6 +82,8 @@ def default_cfg() -> AttrDict:
     c.gs_mesh_trunc = None            # truncation distance of the TSDF (None: 3 voxels)
     c.gs_mesh_min_component = None    # drop the mesh's connected components with fewer faces than this fraction [0, 1] of the largest (None: keep all)
     c.gs_mesh_elevations = None       # extra elevations in degrees, each inside (-90, 90): one more orbit of gs_orbit_views fused per value (None: none)
+    c.gs_mesh_texture = False         # also write the mesh as a textured <stem>_gs_mesh.obj / .mtl / _gs_mesh_tex.png, baked from every fused view
+    c.gs_mesh_texture_patch = 8       # texels per side of the atlas cell two faces share, 4 .. 32
     return c
 
 

@@ -62,6 +62,7 @@ extern "C" int vmv_sizeof(int which) {
         case 108: return (int)sizeof(VmvGsDepthParams);
         case 109: return (int)sizeof(VmvGsTsdfParams);
         case 110: return (int)sizeof(VmvGsMeshComponentsParams);
+        case 111: return (int)sizeof(VmvGsMeshBakeParams);
         default: return (int)op_size(which);
     }
 }

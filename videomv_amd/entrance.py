@@ -405,6 +405,8 @@ def _check_export_cfg(cfg, use_lgm):
     if not cfg.get('gs_mesh'):
         sub = [k for k in ('gs_mesh_extent', 'gs_mesh_trunc', 'gs_mesh_min_component', 'gs_mesh_elevations') if cfg.get(k) is not None]
         sub += ['gs_mesh_res'] if int(cfg.get('gs_mesh_res') or 128) != 128 else []
+        sub += ['gs_mesh_texture'] if cfg.get('gs_mesh_texture') else []
+        sub += ['gs_mesh_texture_patch'] if cfg.get('gs_mesh_texture_patch') not in (None, 8) else []
         if sub:
             raise ValueError(f"{' / '.join(sub)}: a setting of the gs_mesh export: set gs_mesh True")
     else:
@@ -420,6 +422,9 @@ def _check_export_cfg(cfg, use_lgm):
         if elevs is not None and not (isinstance(elevs, (list, tuple))
                                       and all(_is_number(e) and math.isfinite(float(e)) and -90.0 < float(e) < 90.0 for e in elevs)):
             raise ValueError(f"gs_mesh_elevations must be a list of elevations in degrees inside (-90, 90), got {elevs!r}")
+        patch = cfg.get('gs_mesh_texture_patch')
+        if patch is not None and not (isinstance(patch, int) and not isinstance(patch, bool) and 4 <= patch <= 32):
+            raise ValueError(f"gs_mesh_texture_patch must be a whole number of texels in [4, 32], got {patch!r}")
     if not cfg.get('save_gaussians'):
         return
     if not use_lgm:
@@ -452,7 +457,8 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
     (``_gs_orbit_depth.npy`` / ``.png``), the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) and the coloured
     triangle mesh they fuse to (``_gs_mesh.ply``: TSDF fusion + surface nets on the device, gs_mesh.py) are written too;
     ``gs_mesh_elevations`` fuses one more orbit per extra elevation into that mesh (rendered for the fusion alone: no file shows them) and
-    ``gs_mesh_min_component`` drops its small connected components before it is written.  Draws nothing from
+    ``gs_mesh_min_component`` drops its small connected components before it is written; ``gs_mesh_texture`` writes that mesh once more
+    as a textured ``_gs_mesh.obj`` (+ ``.mtl``, ``_gs_mesh_tex.png``) whose texture is baked from every fused view.  Draws nothing from
     the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
     from .gs import GaussianRenderer
     from .lgm import orbit_cameras
@@ -515,13 +521,20 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
             cam_dist = float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
             half = cam_dist * math.sin(0.5 * math.radians(opt.fovy)) if half is None else float(half)
             vol = TsdfVolume(res, half, trunc=None if trunc is None else float(trunc), device=device)
-            vol.integrate(out["median_depth"][0, :, 0], cv[0], renderer.tan_half_fov, colour=_unpremultiplied(out, refiner.bg_color))
+            texture = bool(cfg.get('gs_mesh_texture'))
+            fused = []                                                  # with gs_mesh_texture: (depth, colour, cameras) of every fused orbit, in fusion order
+
+            def fuse(o, cams):
+                depth, colour = o["median_depth"][0, :, 0], _unpremultiplied(o, refiner.bg_color)
+                vol.integrate(depth, cams, renderer.tan_half_fov, colour=colour)
+                if texture:
+                    fused.append((depth, colour, cams.to(depth.device)))
+            fuse(out, cv[0])
             # one more orbit per extra elevation, at the same distance (the default cube is the ball seen whole from that distance, at
             # any elevation): rendered for the fusion alone
             for extra in cfg.get('gs_mesh_elevations') or []:
                 cv_e, cvp_e = orbit_cameras(camera_data, n_orbit, float(extra), camera_dist, opt)
-                out_e = renderer.render_depth(g.to(device), cv_e.to(device), cvp_e.to(device), None, bg_color=bgc)
-                vol.integrate(out_e["median_depth"][0, :, 0], cv_e[0], renderer.tan_half_fov, colour=_unpremultiplied(out_e, refiner.bg_color))
+                fuse(renderer.render_depth(g.to(device), cv_e.to(device), cvp_e.to(device), None, bg_color=bgc), cv_e[0])
             rec['mesh_fused_views'] = vol.n_views
             verts, cols, faces = vol.extract()
             dropped = ""
@@ -535,6 +548,21 @@ def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, cam
             rec['mesh_open_edges'] = mesh_stats(verts, faces)['open_edges']
             logging.info(f"Save mesh ({rec['mesh_vertices']} vertices, {rec['mesh_faces']} faces, {rec['mesh_open_edges']} open edges; "
                          f"{res}^3 voxels of {vol.voxel:.5f}, {rec['mesh_fused_views']} views fused{dropped}) to {rec['mesh_ply']}")
+            if texture and rec['mesh_faces'] == 0:
+                logging.info("gs_mesh_texture: the mesh has no faces, no textured mesh is written")
+            elif texture:
+                # the same mesh as a textured .obj: every fused view's colours blended over the surface (gs_mesh_bake.hip), a texel counted
+                # as seen where it lies within 2 voxels of the view's depth map
+                from .gs_mesh import bake_texture, save_mesh_obj
+                patch = int(cfg.get('gs_mesh_texture_patch') or 8)
+                tex, uv, info = bake_texture(verts, cols, faces, *(torch.cat([f[i] for f in fused]) for i in range(3)), renderer.tan_half_fov,
+                                             patch=patch, depth_tol=2.0 * vol.voxel)
+                rec['mesh_obj'] = stem + '_gs_mesh.obj'
+                save_mesh_obj(verts, faces, uv, tex, stem + '_gs_mesh')
+                rec['mesh_texture_size'], rec['mesh_texels_baked'] = info['size'], info['baked']
+                logging.info(f"Save textured mesh ({info['size']} x {info['size']} texture, patch {patch}, {info['texels']} texels of faces, "
+                             f"{100 * info['baked']:.1f} % baked from {len(fused) * n_orbit} views, {100 * info['fallback']:.1f} % vertex colours) "
+                             f"to {rec['mesh_obj']}")
     return rec
 
 

@@ -5,10 +5,14 @@ and naive surface nets over the fused field, in vectorised torch on the device t
 vertex per sign-changing cell and one quad per sign-changing grid edge; ``mesh_stats`` counts what a consumer would trip over (open and
 misoriented edges, the Euler characteristic, the signed volume); ``mesh_components`` labels the connected components of a mesh
 (``csrc/gs_mesh_cc.hip`` on the device, a torch propagation on the CPU) and ``drop_small_components`` removes the floaters among them;
-``save_mesh_ply`` / ``load_mesh_ply`` are the binary little-endian writer and its inverse.  No RNG anywhere: the same inputs give the
-same file.
+``save_mesh_ply`` / ``load_mesh_ply`` are the binary little-endian writer and its inverse; ``texture_atlas`` lays two faces into every
+P x P cell of a square texture, ``bake_texture`` blends the depth-mapped views over the surface into it (``csrc/gs_mesh_bake.hip`` on the
+device, a torch restatement on the CPU) and ``save_mesh_obj`` / ``load_mesh_obj`` write and read the textured .obj.  No RNG anywhere:
+the same inputs give the same file.
 """
 import ctypes as C
+import math
+import os
 
 import numpy as np
 import torch
@@ -275,3 +279,217 @@ def load_mesh_ply(path):
     if m and not (fr["n"] == 3).all():
         raise ValueError(f"{path}: faces that are not triangles")
     return torch.from_numpy(vr["xyz"].copy()), torch.from_numpy(vr["rgb"].copy()), torch.from_numpy(fr["idx"].astype(np.int64))
+
+
+# ------------------------------------------------------------------------------------------------------------------- UV texture
+MAX_TEXTURE = 8192
+
+
+def _atlas_size(n_faces, patch):
+    """-> (Wc, T) of the atlas of include/vmv.h ("Texture baking"): cells = ceil(m / 2), Wc = ceil(sqrt(cells)), T = P Wc"""
+    m, P = int(n_faces), int(patch)
+    if m < 1 or P < 4:
+        raise ValueError(f"texture atlas: n_faces must be >= 1 and patch >= 4, got {m} and {P}")
+    cells = (m + 1) // 2
+    Wc = math.isqrt(cells - 1) + 1
+    if P * Wc > MAX_TEXTURE:
+        raise ValueError(f"texture atlas: {m} faces at patch {P} need a texture of {P * Wc} px, more than {MAX_TEXTURE}: "
+                         f"choose a smaller patch (gs_mesh_texture_patch) or a smaller gs_mesh_res")
+    return Wc, P * Wc
+
+
+def texture_atlas(n_faces, patch=8):
+    """The closed-form atlas: two faces share every P x P cell of a T x T texture, cell k at column k % Wc, row k // Wc (rows top-down).
+    -> (T, uv [m, 3, 2] fp32): uv[f, corner] = (x, y) in TEXELS (a texel centre is at a half-integer; vt = (x / T, 1 - y / T) in an
+    .obj).  Face 2k's corners sit at the cell's origin + (0.5, 0.5), (P - 2.5, 0.5), (0.5, P - 2.5); face 2k + 1's at the cell's far
+    corner minus those.  Refuses T > 8192."""
+    m, P = int(n_faces), int(patch)
+    Wc, T = _atlas_size(m, P)
+    f = torch.arange(m)
+    k = f // 2
+    origin = torch.stack([(k % Wc) * P, (k // Wc) * P], dim=1).to(torch.float32)                       # [m, 2]
+    tri = torch.tensor([[0.5, 0.5], [P - 2.5, 0.5], [0.5, P - 2.5]], dtype=torch.float32)              # [3, 2]
+    upper = (f % 2 == 1)[:, None, None]
+    return T, origin[:, None, :] + torch.where(upper, float(P) - tri[None], tri[None])
+
+
+def _bake_eager(verts, colours, faces, depth, colour, views, tan_half_fov, patch, T, depth_tol, cos_min, z_min):
+    """The contract of vmv_gs_mesh_bake (include/vmv.h) in fp32 torch on verts' device -> (planes [4, T, T], a face index out of range)."""
+    dev, P, m, n = verts.device, int(patch), int(faces.shape[0]), int(verts.shape[0])
+    V, S = int(depth.shape[0]), int(depth.shape[-1])
+    Wc = T // P
+    y, x = torch.meshgrid(torch.arange(T, device=dev), torch.arange(T, device=dev), indexing="ij")
+    i, j = x % P, y % P
+    upper = (i + j) >= P
+    f = 2 * ((y // P) * Wc + x // P) + upper
+    tri = faces[f.clamp(max=m - 1)]                                     # [T, T, 3]
+    in_range = ((tri >= 0) & (tri < n)).all(-1)
+    owned = (f < m) & in_range
+    bad = (f < m) & ~in_range
+    sel = owned.reshape(-1).nonzero()[:, 0]
+    tri = tri.reshape(-1, 3)[sel]
+    pick = lambda t: t.reshape(-1)[sel].to(torch.float32)
+    sb, tb = pick(torch.where(upper, P - 1 - i, i)), pick(torch.where(upper, P - 1 - j, j))
+    beta, gamma = (sb / float(P - 3)).clamp(0, 1), (tb / float(P - 3)).clamp(0, 1)
+    bg = beta + gamma
+    over = bg > 1
+    beta, gamma = torch.where(over, beta / bg, beta), torch.where(over, gamma / bg, gamma)
+    alpha = 1.0 - beta - gamma
+    v0, v1, v2 = (verts[tri[:, c]] for c in range(3))
+    p = alpha[:, None] * v0 + beta[:, None] * v1 + gamma[:, None] * v2
+    e1, e2 = v1 - v0, v2 - v0                                           # written out (no fused multiply-add): a face that names a vertex twice gives exactly 0
+    nrm = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], dim=1)
+    length = torch.sqrt((nrm * nrm).sum(1))
+    flat = length > 0
+    nrm = nrm / torch.where(flat, length, torch.ones_like(length))[:, None]
+    acc, W = torch.zeros(sel.shape[0], 3, dtype=torch.float32, device=dev), torch.zeros(sel.shape[0], dtype=torch.float32, device=dev)
+    for v in range(V):
+        M = views[v]
+        pc = p @ M[:3, :3] + M[3, :3]                                   # (xv, yv, z)
+        z = pc[:, 2]
+        front = flat & (z > z_min)
+        inv = 1.0 / (torch.where(front, z, torch.ones_like(z)) * tan_half_fov)
+        px, py = ((pc[:, 0] * inv + 1.0) * S - 1.0) * 0.5, ((pc[:, 1] * inv + 1.0) * S - 1.0) * 0.5
+        inside = front & (px >= 0) & (px <= S - 1) & (py >= 0) & (py <= S - 1)
+        px, py = torch.where(inside, px, torch.zeros_like(px)), torch.where(inside, py, torch.zeros_like(py))
+        cos = -((nrm @ M[:3, :3]) * pc).sum(1) / pc.norm(dim=1).clamp_min(1e-30)
+        facing = inside & (cos > cos_min)
+        d = depth[v].reshape(-1)[torch.floor(py + 0.5).long() * S + torch.floor(px + 0.5).long()]
+        hit = facing & (d != 0) & ((d - z).abs() <= depth_tol)
+        x0, y0 = torch.floor(px), torch.floor(py)
+        tx, ty = (px - x0)[None], (py - y0)[None]
+        x0, y0 = x0.long(), y0.long()
+        x1, y1 = (x0 + 1).clamp(max=S - 1), (y0 + 1).clamp(max=S - 1)
+        cm = colour[v].reshape(3, -1)
+        c = ((1.0 - ty) * ((1.0 - tx) * cm[:, y0 * S + x0] + tx * cm[:, y0 * S + x1])
+             + ty * ((1.0 - tx) * cm[:, y1 * S + x0] + tx * cm[:, y1 * S + x1]))                     # [3, N]
+        w = torch.where(hit, cos * cos, torch.zeros_like(cos))
+        acc += torch.where(hit[:, None], w[:, None] * c.t(), torch.zeros_like(acc))
+        W += w
+    c0, c1, c2 = (colours[tri[:, c]] for c in range(3))
+    fallback = alpha[:, None] * c0 + beta[:, None] * c1 + gamma[:, None] * c2
+    rgb = torch.where((W > 0)[:, None], acc / W.clamp_min(1e-30)[:, None], fallback)
+    out = torch.full((4, T * T), 0.5, dtype=torch.float32, device=dev)
+    out[3] = -1.0
+    out[:3, sel] = rgb.t()
+    out[3, sel] = W
+    return out.reshape(4, T, T), bad.any()
+
+
+@torch.no_grad()
+def bake_texture(verts, colours, faces, depth, colour, cam_view, tan_half_fov, patch=8, depth_tol=None, cos_min=0.1, z_min=0.05):
+    """Blend the views ``colour`` [V, 3, S, S] with depth maps ``depth`` [V, S, S] (view depth, 0 = no surface) seen through ``cam_view``
+    [V, 4, 4] (row-vector convention) over the mesh (``verts`` [n, 3], ``colours`` [n, 3], ``faces`` [m, 3] int64) into the atlas of
+    ``texture_atlas(m, patch)``: every texel of a face takes, from each view that sees its surface point within ``depth_tol`` of the
+    view's depth map at an angle with cos > ``cos_min``, the bilinear colour with weight cos^2; a texel no view sees takes the
+    interpolated vertex colours (the contract of vmv_gs_mesh_bake, include/vmv.h).  ``depth_tol`` None: 1 % of the diagonal of the mesh's
+    bounding box.  CUDA tensors run the kernel on the current stream; CPU tensors an fp32 torch restatement of the same definition.
+    -> (texture [4, T, T] fp32 on verts' device: R, G, B and the weight W (0: fell back, -1: no face), uv [m, 3, 2] in texels, info =
+    dict(size, texels (those of a face), baked (the share of them with W > 0), fallback (the share with W == 0)))."""
+    n, m, P = int(verts.shape[0]), int(faces.shape[0]), int(patch)
+    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
+    T, uv = texture_atlas(m, P)
+    if n < 1:
+        raise ValueError("bake_texture: a mesh without vertices")
+    if not 0.0 <= float(cos_min) < 1.0:
+        raise ValueError(f"bake_texture: cos_min must be in [0, 1), got {cos_min}")
+    dev = verts.device
+    V, S = int(depth.shape[0]), int(depth.shape[-1])
+    verts, colours = verts.to(torch.float32).contiguous(), colours.to(dev, torch.float32).contiguous()
+    if depth_tol is None:
+        depth_tol = 0.01 * float((verts.max(0).values - verts.min(0).values).norm())
+    if not float(depth_tol) > 0:
+        raise ValueError(f"bake_texture: depth_tol must be positive, got {depth_tol}")
+    d = depth.to(dev, torch.float32).reshape(V, S, S).contiguous()
+    col = colour.to(dev, torch.float32).reshape(V, 3, S, S).contiguous()
+    views = cam_view.to(dev, torch.float32).reshape(V, 4, 4).contiguous()
+    out_of_range = f"bake_texture: a face names a vertex outside [0, {n})"
+    if dev.type != "cuda":
+        tex, bad = _bake_eager(verts, colours, faces, d, col, views, float(tan_half_fov), P, T, float(depth_tol), float(cos_min), float(z_min))
+        if bool(bad):
+            raise ValueError(out_of_range)
+    else:
+        from .ops import _stream_ptr
+        if not (faces.stride(1) == 1 and faces.stride(0) >= 3):
+            faces = faces.contiguous()
+        tex = torch.empty(4, T, T, dtype=torch.float32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        p = L.GsMeshBakeParams()
+        p.verts, p.vert_colours, p.faces = verts.data_ptr(), colours.data_ptr(), faces.data_ptr()
+        p.face_stride, p.n_faces, p.n_vertices = int(faces.stride(0)), m, n
+        p.depth, p.colour, p.views, p.n_views, p.size, p.tan_half_fov = d.data_ptr(), col.data_ptr(), views.data_ptr(), V, S, float(tan_half_fov)
+        p.z_min, p.depth_tol, p.cos_min, p.patch, p.tex_size = float(z_min), float(depth_tol), float(cos_min), P, T
+        p.out, p.plane_stride, p.status = tex.data_ptr(), T * T, status.data_ptr()
+        L.check(L.load().vmv_gs_mesh_bake(C.byref(p), _stream_ptr()), "gs_mesh_bake")
+        if int(status) & 1:
+            raise ValueError(out_of_range)
+    owned = int((tex[3] >= 0).sum())
+    baked = int((tex[3] > 0).sum())
+    info = dict(size=T, texels=owned, baked=baked / max(owned, 1), fallback=(owned - baked) / max(owned, 1))
+    return tex, uv, info
+
+
+_MATERIAL = "baked"
+
+
+def save_mesh_obj(verts, faces, uv, texture, path):
+    """-> ``path``.obj (v, vt = (x / T, 1 - y / T) per face corner, f a/ta b/tb c/tc, mtllib, usemtl), ``path``.mtl (one material whose
+    map_Kd is the texture) and ``path``_tex.png (the R, G, B planes of ``texture`` [>= 3, T, T] as 8-bit RGB, rounded as save_mesh_ply
+    rounds).  Vertices are not duplicated: an .obj has per-corner UVs.  -> (n, m, T)."""
+    from PIL import Image
+    n, m, T = int(verts.shape[0]), int(faces.shape[0]), int(texture.shape[-1])
+    base = os.path.basename(path)
+    rgb = (texture[:3].detach().float().cpu().clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
+    Image.fromarray(rgb, "RGB").save(path + "_tex.png")
+    with open(path + ".mtl", "w") as fh:
+        fh.write(f"newmtl {_MATERIAL}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {base}_tex.png\n")
+    v = verts.detach().float().cpu().numpy()
+    t = uv.detach().double().cpu().reshape(-1, 2).numpy()
+    f = faces.detach().cpu().numpy() + 1
+    lines = [f"mtllib {base}.mtl", f"usemtl {_MATERIAL}"]
+    lines += ["v %.9g %.9g %.9g" % (a, b, c) for a, b, c in v.tolist()]
+    lines += ["vt %.8f %.8f" % (x / T, 1.0 - y / T) for x, y in t.tolist()]
+    lines += ["f %d/%d %d/%d %d/%d" % (a, 3 * k + 1, b, 3 * k + 2, c, 3 * k + 3) for k, (a, b, c) in enumerate(f.tolist())]
+    with open(path + ".obj", "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return n, m, T
+
+
+def load_mesh_obj(path):
+    """The inverse of ``save_mesh_obj`` -> (verts [n, 3] fp32, faces [m, 3] int64, uv [m, 3, 2] fp32 in texels, texture [T, T, 3] uint8)."""
+    from PIL import Image
+    v, vt, fv, ft, mtl = [], [], [], [], None
+    with open(path + ".obj") as fh:
+        for ln in fh:
+            w = ln.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(x) for x in w[1:4]])
+            elif w[0] == "vt":
+                vt.append([float(x) for x in w[1:3]])
+            elif w[0] == "f":
+                if len(w) != 4:
+                    raise ValueError(f"{path}.obj: faces that are not triangles")
+                pairs = [x.split("/") for x in w[1:]]
+                fv.append([int(a[0]) - 1 for a in pairs])
+                ft.append([int(a[1]) - 1 for a in pairs])
+            elif w[0] == "mtllib":
+                mtl = w[1]
+    if mtl is None:
+        raise ValueError(f"{path}.obj: not a mesh written by save_mesh_obj")
+    image = None
+    with open(os.path.join(os.path.dirname(path), mtl)) as fh:
+        for ln in fh:
+            w = ln.split()
+            if w and w[0] == "map_Kd":
+                image = os.path.join(os.path.dirname(path), w[1])
+    if image is None:
+        raise ValueError(f"{path}.mtl: no map_Kd")
+    tex = torch.from_numpy(np.array(Image.open(image).convert("RGB")))
+    T = int(tex.shape[0])
+    verts = torch.tensor(v, dtype=torch.float64).to(torch.float32).reshape(-1, 3)
+    faces = torch.tensor(fv, dtype=torch.int64).reshape(-1, 3)
+    t = torch.tensor(vt, dtype=torch.float64).reshape(-1, 2)[torch.tensor(ft, dtype=torch.int64).reshape(-1, 3)]
+    uv = torch.stack([t[..., 0] * T, (1.0 - t[..., 1]) * T], dim=-1).to(torch.float32)
+    return verts, faces, uv, tex
