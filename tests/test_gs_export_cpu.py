@@ -169,3 +169,11 @@ def test_entrance_writes_a_loadable_ply_and_nothing_else_changes(monkeypatch, tm
         if f.endswith(".pt"):
             a, b = (torch.load(os.path.join(cfgs[k].log_dir, f)) for k in ("plain", "export"))
             assert torch.equal(a["latent"], b["latent"])
+
+
+def test_the_settings_table_and_the_documented_defaults_agree():
+    """config.default_cfg documents every export key with its default; the table the check and the stages read holds the same value"""
+    from videomv_amd.config import default_cfg
+    from videomv_amd.gs_export import SETTINGS
+    cfg = default_cfg()
+    assert {k: cfg[k] for k in SETTINGS} == {k: s.default for k, s in SETTINGS.items()}

@@ -251,7 +251,8 @@ def test_entrance_writes_a_textured_mesh_and_nothing_else_changes(monkeypatch, t
     from PIL import Image
     plan_interp.install(monkeypatch)
     _install_render_depth(monkeypatch)
-    from videomv_amd import entrance, gs_mesh
+    import videomv_amd.entrance  # noqa: F401
+    from videomv_amd import gs_export, gs_mesh
     from videomv_amd.registry import INFER_ENGINE
     monkeypatch.setattr(TsdfVolume, "integrate", integrate_ref)
     fused, baked, rng = [], [], []
@@ -269,14 +270,14 @@ def test_entrance_writes_a_textured_mesh_and_nothing_else_changes(monkeypatch, t
         baked.append(dict(verts=verts, cols=colours, faces=faces, depth=depth, colour=colour, views=cam_view, tan=tan_half_fov, kw=kw, out=out))
         return out
     monkeypatch.setattr(gs_mesh, "bake_texture", bake_texture_spy)
-    plain_export = entrance._export_gaussians
+    plain_export = gs_export._export_gaussians
 
     def export(*a, **k):
         before = torch.get_rng_state()
         rec = plain_export(*a, **k)
         rng.append(torch.equal(before, torch.get_rng_state()))
         return rec
-    monkeypatch.setattr(entrance, "_export_gaussians", export)
+    monkeypatch.setattr(gs_export, "_export_gaussians", export)
     mesh = BASE + MESH[:-1] + ["32", "gs_mesh_extent", "1.2", "gs_mesh_elevations", "[50]"]
     cfgs, n_fused = {}, {}
     for name, extra in (("plain", []), ("texture", ["gs_mesh_texture", "True"]), ("patch", ["gs_mesh_texture", "True", "gs_mesh_texture_patch", "5"])):

@@ -66,7 +66,7 @@ def _raw(case, verts=None, cols=None, faces=None, depth=None, colour=None, views
 def _rendered_case():
     """real render output: _scene(300, 4) through render_depth at 64 px, 3 views, fused at R = 24 over the cube of half-width 0.6 and
     extracted on the device; baked at patch 8 with a tolerance of 2 voxels; shared, never modified"""
-    from videomv_amd.entrance import _unpremultiplied
+    from videomv_amd.gs_export import _unpremultiplied
     from videomv_amd.gs import GaussianRenderer
     from videomv_amd.gs_mesh import TsdfVolume
     g = _scene(300, 4)

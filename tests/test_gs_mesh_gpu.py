@@ -49,7 +49,7 @@ def _compare(name, acc, case):
 @functools.lru_cache(maxsize=None)
 def _rendered_case():
     """real render output: _scene(300, 4) through render_depth at 64 px, 3 views, fused at R = 24; shared, never modified"""
-    from videomv_amd.entrance import _unpremultiplied
+    from videomv_amd.gs_export import _unpremultiplied
     from videomv_amd.gs import GaussianRenderer
     from videomv_amd.gs_mesh import TsdfVolume
     g = _scene(300, 4)

@@ -146,7 +146,7 @@ def main(argv=None):
             os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
             with open(args.log, "a") as fh:
                 fh.write(line + "\n")
-    from videomv_amd.entrance import _unpremultiplied
+    from videomv_amd.gs_export import _unpremultiplied
     from videomv_amd.gs import GaussianRenderer
     from videomv_amd.gs_mesh import TsdfVolume, mesh_stats
     g = scene(args.gaussians, 1).cuda()

@@ -159,6 +159,9 @@ class GsMeshBakeParams(C.Structure):
                 ("status", C.c_void_p)]
 
 
+MESH_STATUS_RANGE, MESH_STATUS_GAVE_UP = 1, 2      # bits of both status words above (csrc/gs_mesh_common.h)
+
+
 class CopyParams(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
                 ("inner16", C.c_int32), ("ss0", C.c_int64), ("ss1", C.c_int64), ("ss2", C.c_int64)]

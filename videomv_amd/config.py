@@ -64,7 +64,7 @@ def default_cfg() -> AttrDict:
     c.hip_dtype = ''                  # 16-bit storage / MFMA operand type of the HIP kernels: '' (VMV_DTYPE or fp16) | fp16 | bf16
     c.num_views = None                # None -> max_frames
     c.prompt_batch = 1                # t2v entrance: prompts denoised per plan (1 = the reference's one prompt at a time; 2 fills the small levels)
-    # 3-D export of the LGM-refined samples (needs UNet.use_lgm_refine): <stem>_gs.ply (+ orbit renders), entrance._export_gaussians
+    # 3-D export of the LGM-refined samples (needs UNet.use_lgm_refine): <stem>_gs.ply (+ orbit renders), gs_export._export_gaussians
     c.save_gaussians = False          # export a 3-D Gaussian asset for each sample
     c.gs_fit_iters = 0                # iterations fitting the LGM's Gaussians to the generated views (0: the feed-forward Gaussians)
     c.gs_fit_lr_scale = 1.0           # scales the fit's per-group learning rates (gs_fit.DEFAULT_LR)

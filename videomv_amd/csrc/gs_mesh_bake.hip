@@ -11,11 +11,9 @@
 //                       deterministic function of the inputs.
 // The camera rows are indexed by the loop counter alone (wave-uniform: scalar loads).  No load is issued before the test that allows it:
 // the face indices before the vertices, the pixel range before the depth gather, the depth test before the twelve colour taps.
-#include "gemm_common.h"
+#include "gs_mesh_common.h"
 
 namespace {
-
-constexpr int BAKE_STATUS_RANGE = 1;
 
 struct BakeGeom {
     int n_views, size, patch, tex, wc;
@@ -23,15 +21,12 @@ struct BakeGeom {
     long n_faces, n_vertices, face_stride;
 };
 
-__device__ __forceinline__ bool bake_in_range(long v, long n) { return (unsigned long)v < (unsigned long)n; }
-
 __global__ void bake_clear_kernel(int* __restrict__ status) { *status = 0; }
 
 __global__ __launch_bounds__(256) void gs_mesh_bake_kernel(const float* __restrict__ verts, const float* __restrict__ vert_colours,
                                                            const long* __restrict__ faces, const float* __restrict__ depth,
                                                            const float* __restrict__ colour, const float* __restrict__ views, const BakeGeom g,
                                                            float* __restrict__ out, const size_t plane_stride, int* __restrict__ status) {
-#pragma clang fp contract(off)
     const unsigned P = (unsigned)g.patch, PP = P * P, T = (unsigned)g.tex;
     // blocks are dealt round-robin to the 8 XCDs: give each XCD a contiguous run of cells (gemm_common.h) — neighbouring faces of the mesh,
     // which find each other's vertices and pixels in its L2
@@ -43,27 +38,19 @@ __global__ __launch_bounds__(256) void gs_mesh_bake_kernel(const float* __restri
     const unsigned cx = cell % (unsigned)g.wc, cy = cell / (unsigned)g.wc;
     float* const o = out + (size_t)(cy * P + j) * T + (cx * P + i);
     const bool upper = i + j >= P;
-    const long f = 2L * cell + (upper ? 1 : 0);
-    long i0 = 0, i1 = 0, i2 = 0;
-    bool owned = f < g.n_faces;
-    if (owned) {
-        const long* __restrict__ t = faces + f * g.face_stride;
-        i0 = t[0], i1 = t[1], i2 = t[2];
-        if (!(bake_in_range(i0, g.n_vertices) && bake_in_range(i1, g.n_vertices) && bake_in_range(i2, g.n_vertices))) {
-            *status = BAKE_STATUS_RANGE;                               // every writer stores the same word: a plain store
-            owned = false;
-        }
-    }
-    if (!owned) {
+    long vi[3];
+    const int unowned = mesh_load_face(faces, g.face_stride, g.n_faces, g.n_vertices, 2L * cell + (upper ? 1 : 0), vi);
+    if (unowned > 0) *status = MESH_STATUS_RANGE;                      // every writer stores the same word: a plain store
+    if (unowned) {
         o[0] = 0.5f;
         o[plane_stride] = 0.5f;
         o[2 * plane_stride] = 0.5f;
         o[3 * plane_stride] = -1.0f;
         return;
     }
-    const float* __restrict__ a = verts + 3 * i0;
-    const float* __restrict__ b = verts + 3 * i1;
-    const float* __restrict__ c = verts + 3 * i2;
+    const float* __restrict__ a = verts + 3 * vi[0];
+    const float* __restrict__ b = verts + 3 * vi[1];
+    const float* __restrict__ c = verts + 3 * vi[2];
     const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2], cx_ = c[0], cy_ = c[1], cz = c[2];
     // barycentrics of the texel centre in the face's own frame: (s - 0.5, t - 0.5) = (i, j), flipped for the upper face; whole numbers
     const float leg = (float)(P - 3);
@@ -86,18 +73,16 @@ __global__ __launch_bounds__(256) void gs_mesh_bake_kernel(const float* __restri
     float s_r = 0.f, s_g = 0.f, s_b = 0.f, s_w = 0.f;
     for (int v = 0; v < n_views; ++v) {
         const float* __restrict__ m = views + 16 * (size_t)v;          // row-vector convention: [x, 1] @ M
-        const float xv = fmaf(wz, m[8], fmaf(wy, m[4], fmaf(wx, m[0], m[12])));
-        const float yv = fmaf(wz, m[9], fmaf(wy, m[5], fmaf(wx, m[1], m[13])));
-        const float z = fmaf(wz, m[10], fmaf(wy, m[6], fmaf(wx, m[2], m[14])));
+        const auto [xv, yv, z] = mesh_project(m, wx, wy, wz);
         if (!(z > g.z_min)) continue;
         const float inv = 1.0f / (z * g.tan_half_fov);
-        const float px = fmaf(fmaf(xv, inv, 1.0f), fS, -1.0f) * 0.5f, py = fmaf(fmaf(yv, inv, 1.0f), fS, -1.0f) * 0.5f;
+        const float px = mesh_pixel(xv, inv, fS), py = mesh_pixel(yv, inv, fS);
         if (!(px >= 0.0f && px <= hi && py >= 0.0f && py <= hi)) continue;        // false for NaN: every pixel below lies inside the image
         const float ncx = nx * m[0] + ny * m[4] + nz * m[8], ncy = nx * m[1] + ny * m[5] + nz * m[9], ncz = nx * m[2] + ny * m[6] + nz * m[10];
         const float cosv = -(ncx * xv + ncy * yv + ncz * z) / sqrtf(xv * xv + yv * yv + z * z);
         if (!(cosv > g.cos_min)) continue;
         const float* __restrict__ dmap = depth + (size_t)v * SS;
-        const float d = dmap[(size_t)floorf(py + 0.5f) * S + (size_t)floorf(px + 0.5f)];   // px + 0.5 <= size - 0.5: the pixel is <= size - 1
+        const float d = dmap[(size_t)mesh_nearest(py) * S + (size_t)mesh_nearest(px)];   // px + 0.5 <= size - 0.5: the pixel is <= size - 1
         if (d == 0.0f || fabsf(d - z) > g.depth_tol) continue;
         const float fx0 = floorf(px), fy0 = floorf(py);
         const float tx = px - fx0, ty = py - fy0;
@@ -118,9 +103,9 @@ __global__ __launch_bounds__(256) void gs_mesh_bake_kernel(const float* __restri
         o[2 * plane_stride] = s_b / s_w;
         o[3 * plane_stride] = s_w;
     } else {                                                           // no view sees the texel: the interpolated vertex colours
-        const float* __restrict__ ca = vert_colours + 3 * i0;
-        const float* __restrict__ cb = vert_colours + 3 * i1;
-        const float* __restrict__ cc = vert_colours + 3 * i2;
+        const float* __restrict__ ca = vert_colours + 3 * vi[0];
+        const float* __restrict__ cb = vert_colours + 3 * vi[1];
+        const float* __restrict__ cc = vert_colours + 3 * vi[2];
         o[0] = alpha * ca[0] + beta * cb[0] + gamma * cc[0];
         o[plane_stride] = alpha * ca[1] + beta * cb[1] + gamma * cc[1];
         o[2 * plane_stride] = alpha * ca[2] + beta * cb[2] + gamma * cc[2];
@@ -134,8 +119,9 @@ extern "C" int vmv_gs_mesh_bake(const VmvGsMeshBakeParams* pp, void* stream) {
     if (!pp) return VMV_ENULL;
     const VmvGsMeshBakeParams& p = *pp;
     if (!p.verts || !p.vert_colours || !p.faces || !p.depth || !p.colour || !p.views || !p.out || !p.status) return VMV_ENULL;
-    if (p.n_faces < 1 || p.n_vertices < 1 || p.face_stride < 3 || p.n_views < 1 || p.size < 1 || p.patch < 4) return VMV_EINVAL;
-    if (!(p.tan_half_fov > 0.f) || !(p.z_min > 0.f) || !(p.depth_tol > 0.f) || !(p.cos_min >= 0.f && p.cos_min < 1.f)) return VMV_EINVAL;
+    const int ef = mesh_check_faces(p.faces, p.face_stride, p.n_faces, 1, p.n_vertices);
+    const int ev = mesh_check_views(p.depth, p.colour, p.views, p.n_views, p.size, p.tan_half_fov, p.z_min);
+    if (ef == VMV_EINVAL || ev == VMV_EINVAL || p.patch < 4 || !(p.depth_tol > 0.f) || !(p.cos_min >= 0.f && p.cos_min < 1.f)) return VMV_EINVAL;
     // the atlas in 64 bits: Wc = ceil(sqrt(ceil(n_faces / 2))), whatever n_faces is
     const int64_t cells = p.n_faces / 2 + p.n_faces % 2;
     int64_t wc = (int64_t)sqrt((double)cells);
@@ -143,11 +129,8 @@ extern "C" int vmv_gs_mesh_bake(const VmvGsMeshBakeParams* pp, void* stream) {
     while (wc > 1 && (wc - 1) * (wc - 1) >= cells) --wc;
     if ((int64_t)p.tex_size != (int64_t)p.patch * wc) return VMV_EINVAL;
     if (p.plane_stride < (int64_t)p.tex_size * p.tex_size) return VMV_EINVAL;
-    if (p.tex_size > 8192 || p.size > 32768 || p.n_faces > 0x7fffffffL || p.n_vertices > 0x7fffffffL) return VMV_ERANGE;
-    if (((uintptr_t)p.faces & 7) ||
-        (((uintptr_t)p.verts | (uintptr_t)p.vert_colours | (uintptr_t)p.depth | (uintptr_t)p.colour | (uintptr_t)p.views | (uintptr_t)p.out |
-          (uintptr_t)p.status) & 3))
-        return VMV_EALIGN;
+    if (ef == VMV_ERANGE || ev == VMV_ERANGE || p.tex_size > 8192) return VMV_ERANGE;
+    if (ef || ev || (((uintptr_t)p.verts | (uintptr_t)p.vert_colours | (uintptr_t)p.out | (uintptr_t)p.status) & 3)) return VMV_EALIGN;
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const BakeGeom g{p.n_views, p.size, p.patch, p.tex_size, (int)wc, p.tan_half_fov, p.z_min, p.depth_tol, p.cos_min,
                      (long)p.n_faces, (long)p.n_vertices, (long)p.face_stride};

@@ -14,11 +14,10 @@
 // kept in a register must not keep a loop alive); every parent write in the hook pass is an agent-scope atomic.
 // Every loop spends from one per-thread budget of steps; a thread that runs out sets bit 1 of the status word and leaves, and a
 // thread that starts after that leaves at once: a parent array that something else corrupted ends the kernel, it cannot hang it.
-#include "common.h"
+#include "gs_mesh_common.h"
 
 namespace {
 
-constexpr int CC_STATUS_RANGE = 1, CC_STATUS_GAVE_UP = 2;
 // A chain strictly decreases, so no walk of a sound parent array is longer than n_vertices, and a halving walk takes two links per
 // step: the budget of a thread is 2 min(n_vertices, CC_MAX_STEPS) + CC_SLACK steps, four full-length walks and the retries of its two
 // unions.  A walk also leaves at the first parent that is larger than its slot (or negative): the invariant itself is checked.
@@ -67,8 +66,6 @@ __device__ __forceinline__ bool cc_union(int* parent, int a, int b, int& budget)
     return true;
 }
 
-__device__ __forceinline__ bool cc_in_range(long v, long n) { return (unsigned long)v < (unsigned long)n; }
-
 __global__ __launch_bounds__(256) void cc_init_kernel(int* __restrict__ label, int* __restrict__ face_count, int* __restrict__ status, const long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) *status = 0;
@@ -79,17 +76,12 @@ __global__ __launch_bounds__(256) void cc_init_kernel(int* __restrict__ label, i
 
 __global__ __launch_bounds__(256) void cc_hook_kernel(const long* __restrict__ faces, const long stride, const long n_faces, const long n,
                                                       int* parent, int* status, const int steps) {
-    const long f = (long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= n_faces) return;
-    const long* __restrict__ t = faces + f * stride;
-    const long v0 = t[0], v1 = t[1], v2 = t[2];
-    if (!(cc_in_range(v0, n) && cc_in_range(v1, n) && cc_in_range(v2, n))) {       // before any access that uses an index
-        atomicOr(status, CC_STATUS_RANGE);
-        return;
-    }
-    if (cc_load(status) & CC_STATUS_GAVE_UP) return;
+    long v[3];
+    const int bad = mesh_load_face(faces, stride, n_faces, n, (long)blockIdx.x * 256 + threadIdx.x, v);
+    if (bad > 0) atomicOr(status, MESH_STATUS_RANGE);
+    if (bad || (cc_load(status) & MESH_STATUS_GAVE_UP)) return;
     int budget = steps;
-    if (!(cc_union(parent, (int)v0, (int)v1, budget) && cc_union(parent, (int)v0, (int)v2, budget))) atomicOr(status, CC_STATUS_GAVE_UP);
+    if (!(cc_union(parent, (int)v[0], (int)v[1], budget) && cc_union(parent, (int)v[0], (int)v[2], budget))) atomicOr(status, MESH_STATUS_GAVE_UP);
 }
 
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int* status, const long n, const int steps) {
@@ -99,7 +91,7 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int* statu
     // no halving here: the only write to a slot is its own final root, so a reader sees either the old parent or the root, both ancestors
     const int r = cc_root<false>(parent, (int)i, budget);
     if (r < 0) {
-        atomicOr(status, CC_STATUS_GAVE_UP);
+        atomicOr(status, MESH_STATUS_GAVE_UP);
         return;
     }
     __hip_atomic_store(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -107,15 +99,11 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int* statu
 
 __global__ __launch_bounds__(256) void cc_count_kernel(const long* __restrict__ faces, const long stride, const long n_faces, const long n,
                                                        const int* __restrict__ label, int* __restrict__ face_count) {
-    const long f = (long)blockIdx.x * 256 + threadIdx.x;
     int r = -1;                                                        // this face's label; -1: nothing (left) to count
-    if (f < n_faces) {
-        const long* __restrict__ t = faces + f * stride;
-        const long v0 = t[0], v1 = t[1], v2 = t[2];
-        if (cc_in_range(v0, n) && cc_in_range(v1, n) && cc_in_range(v2, n)) {
-            r = label[v0];
-            if (!cc_in_range(r, n)) r = -1;                            // a label is in range unless the array was corrupted
-        }
+    long v[3];
+    if (mesh_load_face(faces, stride, n_faces, n, (long)blockIdx.x * 256 + threadIdx.x, v) == 0) {
+        r = label[v[0]];
+        if (!mesh_in_range(r, n)) r = -1;                              // a label is in range unless the array was corrupted
     }
     // One add per face onto the label's slot is one contended address for a whole component (measured: 808 k faces, 775 k of them in
     // one component: 0.7-8.8 ms in this pass alone).  So the wave adds once per label it holds, and the label its first lane holds (in a
@@ -161,9 +149,8 @@ extern "C" int vmv_gs_mesh_components(const VmvGsMeshComponentsParams* pp, void*
     if (!pp) return VMV_ENULL;
     const VmvGsMeshComponentsParams& p = *pp;
     if (!p.faces || !p.label || !p.face_count || !p.status) return VMV_ENULL;
-    if (p.n_vertices < 1 || p.n_faces < 0 || p.face_stride < 3) return VMV_EINVAL;
-    if (p.n_vertices > 0x7fffffffL || p.n_faces > 0x7fffffffL) return VMV_ERANGE;      // int32 labels; one thread per face
-    if (((uintptr_t)p.faces & 7) || (((uintptr_t)p.label | (uintptr_t)p.face_count | (uintptr_t)p.status) & 3)) return VMV_EALIGN;
+    if (const int e = mesh_check_faces(p.faces, p.face_stride, p.n_faces, 0, p.n_vertices)) return e;
+    if (((uintptr_t)p.label | (uintptr_t)p.face_count | (uintptr_t)p.status) & 3) return VMV_EALIGN;
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long n = p.n_vertices, m = p.n_faces;
     const int steps = 2 * (int)(n < CC_MAX_STEPS ? n : CC_MAX_STEPS) + CC_SLACK;

@@ -8,8 +8,8 @@
 // projections and their depth gathers, each issued at a pixel clamped into the image whether or not the view will count, then the
 // definition's branches over the four values in view order — four independent gathers in flight per thread instead of one behind a
 // branch (written as one loop the compiler moved the load under the visibility test and waited for it there).  The colour gather
-// stays behind its branch: only voxels inside the truncation band take it.  One reciprocal of z tan serves both pixel coordinates.
-#include "gemm_common.h"
+// stays behind its branch: only voxels inside the truncation band take it.  Projection and pixel mapping: gs_mesh_common.h.
+#include "gs_mesh_common.h"
 
 namespace {
 
@@ -23,7 +23,6 @@ struct TsdfGeom {
 __global__ __launch_bounds__(256) void gs_tsdf_integrate_kernel(const float* __restrict__ depth, const float* __restrict__ colour,
                                                                 const float* __restrict__ views, const TsdfGeom g, float* __restrict__ acc,
                                                                 const size_t plane_stride) {
-#pragma clang fp contract(off)
     const unsigned R = (unsigned)g.res;
     // blocks are dealt round-robin to the 8 XCDs: give each XCD a contiguous slab of the volume (gemm_common.h), so that the voxel rows
     // it works on at one time are neighbours and find each other's depth-map lines in its L2
@@ -52,15 +51,9 @@ __global__ __launch_bounds__(256) void gs_tsdf_integrate_kernel(const float* __r
 #pragma unroll
         for (int j = 0; j < TS_BATCH; ++j) {
             const int v = min(v0 + j, g.n_views - 1);                  // past the last view: that view again, masked out below
-            const float* __restrict__ m = views + 16 * (size_t)v;      // row-vector convention: [x, 1] @ M
-            // explicit fused multiply-adds, contraction off: the same instructions at every position of the batch, so a view gives the
-            // same bits wherever a call's split puts it
-            const float xv = fmaf(wz, m[8], fmaf(wy, m[4], fmaf(wx, m[0], m[12])));
-            const float yv = fmaf(wz, m[9], fmaf(wy, m[5], fmaf(wx, m[1], m[13])));
-            const float z = fmaf(wz, m[10], fmaf(wy, m[6], fmaf(wx, m[2], m[14])));
+            const auto [xv, yv, z] = mesh_project(views + 16 * (size_t)v, wx, wy, wz);
             const float inv = 1.0f / (z * g.tan_half_fov);
-            const float fx = floorf(fmaf(fmaf(fmaf(xv, inv, 1.0f), fS, -1.0f), 0.5f, 0.5f));
-            const float fy = floorf(fmaf(fmaf(fmaf(yv, inv, 1.0f), fS, -1.0f), 0.5f, 0.5f));
+            const float fx = mesh_nearest(mesh_pixel(xv, inv, fS)), fy = mesh_nearest(mesh_pixel(yv, inv, fS));
             // the range test on the floats (a voxel near the camera plane gives an enormous or a NaN pixel); false for NaN
             seen[j] = v0 + j < g.n_views && z > g.z_min && fx >= 0.0f && fx < fS && fy >= 0.0f && fy < fS;
             // fmaxf / fminf return the other operand for a NaN: the clamped pixel is always inside the image
@@ -111,11 +104,12 @@ extern "C" int vmv_gs_tsdf_integrate(const VmvGsTsdfParams* pp, void* stream) {
     const VmvGsTsdfParams& p = *pp;
     if (!p.depth || !p.views || !p.acc) return VMV_ENULL;
     if (p.n_views < 1 || p.size < 1 || p.res < 2 || p.res > 1024) return VMV_EINVAL;
-    if (p.size > 32768) return VMV_ERANGE;                             // the kernel's 32-bit pixel offsets
-    if (!(p.tan_half_fov > 0.f) || !(p.voxel > 0.f) || !(p.trunc > 0.f) || !(p.z_min > 0.f)) return VMV_EINVAL;
+    if (p.size > MESH_MAX_VIEW_SIZE) return VMV_ERANGE;                // this entry point refuses the size before the values, as it always has
+    const int ev = mesh_check_views(p.depth, p.colour, p.views, p.n_views, p.size, p.tan_half_fov, p.z_min);
+    if (ev == VMV_EINVAL || !(p.voxel > 0.f) || !(p.trunc > 0.f)) return VMV_EINVAL;
     const long n = (long)p.res * p.res * p.res;
     if (p.plane_stride < n) return VMV_EINVAL;
-    if (((uintptr_t)p.depth | (uintptr_t)p.colour | (uintptr_t)p.views | (uintptr_t)p.acc) & 3) return VMV_EALIGN;
+    if (ev || ((uintptr_t)p.acc & 3)) return ev ? ev : VMV_EALIGN;
     const TsdfGeom g{p.n_views, p.size, p.res, p.carve ? 1 : 0, p.tan_half_fov, p.origin[0], p.origin[1], p.origin[2], p.voxel, p.trunc, p.z_min};
     hipLaunchKernelGGL(gs_tsdf_integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        p.depth, p.colour, p.views, g, p.acc, (size_t)p.plane_stride);

@@ -12,7 +12,6 @@ plus a ``.pt`` tensor and a PNG contact sheet; the second, LGM-refined loop (:27
 runs when ``UNet.use_lgm_refine`` is set (also under ``frame_parallel``; not under ``cfg_parallel``).
 """
 import logging
-import math
 import os
 import os.path as osp
 import re
@@ -27,6 +26,8 @@ from .camera import entrance_camera_data
 from .pipeline import sample_views
 from .dist import rank_seed, shard_prompts
 from . import embedder as _embedder  # noqa: F401  (registers the embedders)
+from . import gs_export
+from .video_io import _save_contact_sheet, _save_frames_safe, save_video_frames  # noqa: F401  (save_video_frames: the writer's public name)
 
 
 def _plain(d):
@@ -91,7 +92,7 @@ def worker(gpu, cfg, cfg_update):
     cfg.rank = cfg.pmi_rank
     # frame_parallel (not a reference key; BASELINE configs[2]): the ranks share ONE sample — same seed, F / N views each
     fpar = bool(cfg.get('frame_parallel', False)) and cfg.world_size > 1
-    _check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')) and not (fpar and bool(cfg.get('cfg_parallel', False))))
+    gs_export._check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')) and not (fpar and bool(cfg.get('cfg_parallel', False))))
     torch.manual_seed(cfg.seed if fpar else rank_seed(cfg.seed, cfg.rank))
     on_gpu = str(cfg.device).startswith("cuda")
     device = torch.device("cuda", gpu) if on_gpu else torch.device(cfg.device)
@@ -174,24 +175,11 @@ def worker(gpu, cfg, cfg_update):
             video_gs_all = decode_views(autoencoder, x0_gs_all, int(cfg.decoder_bs), cfg.scale_factor)
         if fpar and cfg.rank != 0:          # every rank holds the gathered views; rank 0 writes them
             return
+        export = lambda video_gs, path: gs_export._export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist, path, device)
         for s, (idx, caption) in enumerate(group):
-            x0, video = x0_all[s:s + 1], video_all[s:s + 1]
-            x0_gs, video_gs = (None, None) if video_gs_all is None else (x0_gs_all[s:s + 1], video_gs_all[s:s + 1])
             cap_name = re.sub(r'[^\w\s]', '', caption).replace(' ', '_')
-            stem = f'rank_{cfg.world_size:02d}_{cfg.rank:02d}_{idx:04d}_{cap_name}_{int(elevation):02d}_{camera_dist:.02f}'
-            path = osp.join(cfg.log_dir, stem + '.pt')
-            torch.save({'latent': x0.cpu(), 'video': video.cpu(), 'caption': caption}, path)
-            _save_contact_sheet(video.cpu(), osp.join(cfg.log_dir, stem + '.png'), cfg.mean, cfg.std)
-            _save_frames_safe(osp.join(cfg.log_dir, stem + '.mp4'), video, cfg)          # the reference's <name>.mp4 + frame PNGs
-            if video_gs is not None:                     # the reference's second file: <name>_gs
-                torch.save({'latent': x0_gs.cpu(), 'video': video_gs.cpu(), 'caption': caption}, osp.join(cfg.log_dir, stem + '_gs.pt'))
-                _save_contact_sheet(video_gs.cpu(), osp.join(cfg.log_dir, stem + '_gs.png'), cfg.mean, cfg.std)
-                _save_frames_safe(osp.join(cfg.log_dir, stem + '_gs.mp4'), video_gs, cfg)
-                if cfg.get('save_gaussians'):
-                    gs_exports.append(_export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist,
-                                                        osp.join(cfg.log_dir, stem), device))
-            logging.info('Save views to %s' % path)
-            outputs.append(path)
+            name = f'{idx:04d}_{cap_name}_{int(elevation):02d}_{camera_dist:.02f}'
+            _write_sample(cfg, name, {'caption': caption}, s, (x0_all, video_all), (x0_gs_all, video_gs_all), export, outputs, gs_exports)
 
     pending = []
     for idx, caption in enumerate(test_list):
@@ -207,6 +195,29 @@ def worker(gpu, cfg, cfg_update):
             pending = []
     if pending:
         run_group(pending)
+    return _finish(cfg, model, on_gpu, outputs, gs_exports)
+
+
+def _write_sample(cfg, name, source, s, plain, refined, export, outputs, gs_exports):
+    """Sample ``s`` of a group's (latents, videos) ``plain``: ``<stem>.pt`` (with ``source``: the caption or the image's path), the sheet, the
+    reference's <stem>.mp4 + frame PNGs; the same as ``<stem>_gs`` for ``refined`` (the LGM-refined loop: the reference's second file),
+    and with ``save_gaussians`` their 3-D asset, ``export(video_gs, stem)``."""
+    stem = osp.join(cfg.log_dir, f'rank_{cfg.world_size:02d}_{cfg.rank:02d}_{name}')
+    for tag, (x0, video) in (('', plain), ('_gs', refined)):
+        if video is None:
+            continue
+        x0, video = x0[s:s + 1], video[s:s + 1]
+        torch.save({'latent': x0.cpu(), 'video': video.cpu(), **source}, stem + tag + '.pt')
+        _save_contact_sheet(video.cpu(), stem + tag + '.png', cfg.mean, cfg.std)
+        _save_frames_safe(stem + tag + '.mp4', video, cfg)
+        if tag and cfg.get('save_gaussians'):
+            gs_exports.append(export(video, stem))
+    logging.info('Save views to %s' % (stem + '.pt'))
+    outputs.append(stem + '.pt')
+
+
+def _finish(cfg, model, on_gpu, outputs, gs_exports):
+    """The end of both workers: wait for the device, close the process group, hand the written paths over in ``cfg``."""
     logging.info('Congratulations! The inference is completed!')
     if on_gpu:
         torch.cuda.synchronize()
@@ -260,7 +271,7 @@ def worker_i2v(gpu, cfg, cfg_update):
         cfg = AttrDict(assign_signle_cfg(cfg, cfg_update, 'vldm_cfg'))
         merge_into(cfg, _plain(dict(cfg_update)))
     cfg.gpu, cfg.seed, cfg.rank = gpu, int(cfg.seed), cfg.pmi_rank
-    _check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')))
+    gs_export._check_export_cfg(cfg, bool(dict(cfg.UNet).get('use_lgm_refine')))
     if cfg.get('hip_dtype'):                        # (not a reference key) 16-bit storage type of the kernels: fp16 | bf16
         from . import _lib
         _lib.set_elem(cfg.hip_dtype)
@@ -339,23 +350,10 @@ def worker_i2v(gpu, cfg, cfg_update):
             x0_gs_all = diffusion.ddim_sample_loop(noise=noise, model=model, autoencoder=autoencoder, model_kwargs=kw_gs,
                                                    guide_scale=cfg.guide_scale, ddim_timesteps=int(cfg.ddim_timesteps), eta=0.0)
             video_gs_all = decode_views(autoencoder, x0_gs_all, int(cfg.decoder_bs), cfg.scale_factor)
+        export = lambda video_gs, path: gs_export._export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist, path, device)
         for s_, (idx, line, _) in enumerate(group):
-            x0, video = x0_all[s_:s_ + 1], video_all[s_:s_ + 1]
-            x0_gs, video_gs = (None, None) if video_gs_all is None else (x0_gs_all[s_:s_ + 1], video_gs_all[s_:s_ + 1])
-            stem = f'rank_{cfg.world_size:02d}_{cfg.rank:02d}_{idx:04d}_{osp.basename(line).split(".")[0]}_{int(elevation):02d}_{camera_dist:.02f}'
-            path = osp.join(cfg.log_dir, stem + '.pt')
-            torch.save({'latent': x0.cpu(), 'video': video.cpu(), 'image': line}, path)
-            _save_contact_sheet(video.cpu(), osp.join(cfg.log_dir, stem + '.png'), cfg.mean, cfg.std)
-            _save_frames_safe(osp.join(cfg.log_dir, stem + '.mp4'), video, cfg)
-            if video_gs is not None:
-                torch.save({'latent': x0_gs.cpu(), 'video': video_gs.cpu(), 'image': line}, osp.join(cfg.log_dir, stem + '_gs.pt'))
-                _save_contact_sheet(video_gs.cpu(), osp.join(cfg.log_dir, stem + '_gs.png'), cfg.mean, cfg.std)
-                _save_frames_safe(osp.join(cfg.log_dir, stem + '_gs.mp4'), video_gs, cfg)
-                if cfg.get('save_gaussians'):
-                    gs_exports.append(_export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist,
-                                                        osp.join(cfg.log_dir, stem), device))
-            logging.info('Save views to %s' % path)
-            outputs.append(path)
+            name = f'{idx:04d}_{osp.basename(line).split(".")[0]}_{int(elevation):02d}_{camera_dist:.02f}'
+            _write_sample(cfg, name, {'image': line}, s_, (x0_all, video_all), (x0_gs_all, video_gs_all), export, outputs, gs_exports)
 
     pending = []
     for idx, line in enumerate(test_list):
@@ -376,294 +374,4 @@ def worker_i2v(gpu, cfg, cfg_update):
             pending = []
     if pending:
         run_group(pending)
-    logging.info('Congratulations! The inference is completed!')
-    if on_gpu:
-        torch.cuda.synchronize()
-    if cfg.world_size > 1:
-        fc = getattr(getattr(model, "module", model), "frame_comm", None)
-        if fc is not None and hasattr(fc, "close"):
-            fc.close()              # the native RCCL communicators (and twins) go first: collective, every rank gets here
-        dist.barrier()
-        dist.destroy_process_group()
-    cfg.outputs = outputs
-    if cfg.get('save_gaussians'):
-        cfg.gs_exports = gs_exports
-    return cfg
-
-
-def _check_export_cfg(cfg, use_lgm):
-    """`save_gaussians` (not a reference key) exports the LGM-refined loop's Gaussians: refuse it, before any sampling, where that loop
-    does not run or cannot run (the LGM renders square views only), or where the fit's objective is not one the fitter knows."""
-    geometry = [k for k in ('gs_orbit_depth', 'gs_points', 'gs_points_voxel', 'gs_mesh') if cfg.get(k)]
-    if geometry and not (cfg.get('save_gaussians') and int(cfg.get('gs_orbit_views') or 0) > 0):
-        raise ValueError(f"{' / '.join(geometry)}: depth maps, the point cloud and the mesh come from the orbit render of the exported "
-                         "Gaussians: set save_gaussians True and gs_orbit_views > 0")
-    if cfg.get('gs_points_voxel') and not cfg.get('gs_points'):
-        raise ValueError("gs_points_voxel is the voxel size of the gs_points export: set gs_points True")
-    if cfg.get('gs_points_voxel') is not None and cfg.get('gs_points') and not float(cfg.get('gs_points_voxel')) > 0:
-        raise ValueError(f"gs_points_voxel must be positive, got {cfg.get('gs_points_voxel')}")
-    if not cfg.get('gs_mesh'):
-        sub = [k for k in ('gs_mesh_extent', 'gs_mesh_trunc', 'gs_mesh_min_component', 'gs_mesh_elevations') if cfg.get(k) is not None]
-        sub += ['gs_mesh_res'] if int(cfg.get('gs_mesh_res') or 128) != 128 else []
-        sub += ['gs_mesh_texture'] if cfg.get('gs_mesh_texture') else []
-        sub += ['gs_mesh_texture_patch'] if cfg.get('gs_mesh_texture_patch') not in (None, 8) else []
-        if sub:
-            raise ValueError(f"{' / '.join(sub)}: a setting of the gs_mesh export: set gs_mesh True")
-    else:
-        if not 16 <= int(cfg.get('gs_mesh_res') or 128) <= 512:
-            raise ValueError(f"gs_mesh_res must be in [16, 512], got {cfg.get('gs_mesh_res')}")
-        for k in ('gs_mesh_extent', 'gs_mesh_trunc'):
-            if cfg.get(k) is not None and not float(cfg.get(k)) > 0:
-                raise ValueError(f"{k} must be positive, got {cfg.get(k)}")
-        frac = cfg.get('gs_mesh_min_component')
-        if frac is not None and not (_is_number(frac) and 0.0 <= float(frac) <= 1.0):
-            raise ValueError(f"gs_mesh_min_component must be a fraction in [0, 1] of the largest component's faces, got {frac!r}")
-        elevs = cfg.get('gs_mesh_elevations')
-        if elevs is not None and not (isinstance(elevs, (list, tuple))
-                                      and all(_is_number(e) and math.isfinite(float(e)) and -90.0 < float(e) < 90.0 for e in elevs)):
-            raise ValueError(f"gs_mesh_elevations must be a list of elevations in degrees inside (-90, 90), got {elevs!r}")
-        patch = cfg.get('gs_mesh_texture_patch')
-        if patch is not None and not (isinstance(patch, int) and not isinstance(patch, bool) and 4 <= patch <= 32):
-            raise ValueError(f"gs_mesh_texture_patch must be a whole number of texels in [4, 32], got {patch!r}")
-    if not cfg.get('save_gaussians'):
-        return
-    if not use_lgm:
-        raise ValueError("save_gaussians needs the LGM-refined loop: set UNet.use_lgm_refine True (and no cfg_parallel)")
-    if int(cfg.resolution[0]) != int(cfg.resolution[1]):
-        raise ValueError(f"save_gaussians: the LGM branch renders square views, resolution {list(cfg.resolution)} is not square")
-    from .gs_fit import check_loss
-    try:
-        check_loss(*_fit_loss(cfg))
-    except ValueError as e:
-        raise ValueError(f"save_gaussians: gs_fit_loss / gs_fit_lambda_dssim: {e}") from None
-
-
-def _is_number(x):
-    return isinstance(x, (int, float)) and not isinstance(x, bool)
-
-
-def _fit_loss(cfg):
-    """-> (gs_fit_loss, gs_fit_lambda_dssim) with their defaults"""
-    lam = cfg.get('gs_fit_lambda_dssim')
-    return str(cfg.get('gs_fit_loss') or 'mse'), 0.2 if lam is None else float(lam)
-
-
-@torch.no_grad()
-def _export_gaussians(cfg, model, video_gs, camera_data, gs_data, elevation, camera_dist, stem, device):
-    """The 3-D asset of one LGM-refined sample: the LGM on its final key views (LgmRefiner.gaussians_from_views), optionally fitted to
-    all its decoded views (gs_fit.GaussianFitter: targets video * 0.5 + 0.5 against the refiner's background), written as
-    ``<stem>_gs.ply``; with ``gs_orbit_views`` also ``<stem>_gs_orbit.png`` and the frames / mp4 of that orbit; with ``gs_orbit_depth``
-    / ``gs_points`` / ``gs_mesh`` that orbit is rendered ONCE in the rasteriser's depth mode and its median-depth maps
-    (``_gs_orbit_depth.npy`` / ``.png``), the voxel-merged coloured point cloud they unproject to (``_gs_points.ply``) and the coloured
-    triangle mesh they fuse to (``_gs_mesh.ply``: TSDF fusion + surface nets on the device, gs_mesh.py) are written too;
-    ``gs_mesh_elevations`` fuses one more orbit per extra elevation into that mesh (rendered for the fusion alone: no file shows them) and
-    ``gs_mesh_min_component`` drops its small connected components before it is written; ``gs_mesh_texture`` writes that mesh once more
-    as a textured ``_gs_mesh.obj`` (+ ``.mtl``, ``_gs_mesh_tex.png``) whose texture is baked from every fused view.  Draws nothing from
-    the torch RNG (the next prompt's noise stays the same).  -> dict of paths and fit statistics (cfg.gs_exports)."""
-    from .gs import GaussianRenderer
-    from .lgm import orbit_cameras
-    refiner = model.lgm_refiner(device)
-    opt = refiner.opt
-    F_ = video_gs.shape[2]
-    idxs = [0, 6, 12, 18] if F_ == 24 else [i * F_ // 4 for i in range(4)]
-    views = video_gs[0].permute(1, 0, 2, 3).to(device, torch.float32)                 # [F, 3, H, W] in [-1, 1]
-    g = refiner.gaussians_from_views(views[idxs].contiguous(), gs_data)              # [1, N, 14]
-    rec = dict(ply=stem + '_gs.ply', fit_iters=int(cfg.get('gs_fit_iters') or 0))
-    if rec['fit_iters'] > 0:
-        from .gs_fit import GaussianFitter
-        bg = (refiner.bg_color,) * 3
-        loss, lam = _fit_loss(cfg)
-        fitter = GaussianFitter(g[0], gs_data['cam_view'][0], gs_data['cam_view_proj'][0], (views * 0.5 + 0.5).contiguous(), bg=bg,
-                                lr_scale=float(cfg.get('gs_fit_lr_scale') or 1.0), fovy=opt.fovy, znear=opt.znear, zfar=opt.zfar,
-                                loss=loss, lambda_dssim=lam)
-        st = fitter.fit(rec['fit_iters'])
-        g = fitter.gaussians().unsqueeze(0)
-        rec.update(st)
-        logging.info(f"gs fit: {rec['fit_iters']} iterations on {F_} views, PSNR {st['psnr_before']:.2f} -> {st['psnr_after']:.2f} dB "
-                     f"(loss {st['loss_before']:.3e} -> {st['loss_after']:.3e})"
-                     + (f", SSIM {st['ssim_before']:.4f} -> {st['ssim_after']:.4f}" if 'ssim_after' in st else "")
-                     + f", {st['ms_per_iter']:.2f} ms/iteration, "
-                     f"{st['instances']} instances")
-    rec['vertices'] = refiner.renderer.save_ply(g, rec['ply'])
-    logging.info(f"Save 3D Gaussians ({rec['vertices']} of {g.shape[1]}) to {rec['ply']}")
-    n_orbit = int(cfg.get('gs_orbit_views') or 0)
-    if n_orbit > 0:
-        elev = cfg.get('gs_orbit_elevation')
-        elev = elevation if elev is None else float(elev)
-        size = int(cfg.get('gs_orbit_size') or opt.output_size)
-        cv, cvp = orbit_cameras(camera_data, n_orbit, elev, camera_dist, opt)
-        bgc = torch.full((3,), refiner.bg_color, dtype=torch.float32, device=device)
-        renderer = GaussianRenderer(size, opt.fovy, opt.znear, opt.zfar)
-        geometry = bool(cfg.get('gs_orbit_depth') or cfg.get('gs_points') or cfg.get('gs_mesh'))
-        out = (renderer.render_depth if geometry else renderer.render)(g.to(device), cv.to(device), cvp.to(device), None, bg_color=bgc)
-        img = out["image"]
-        mean, std = torch.tensor(cfg.mean).view(1, 3, 1, 1, 1), torch.tensor(cfg.std).view(1, 3, 1, 1, 1)
-        video = (img.float().cpu().permute(0, 2, 1, 3, 4) - mean) / std                 # [1, 3, n, S, S], the entrance's range
-        rec['orbit_sheet'], rec['orbit_frames'] = stem + '_gs_orbit.png', stem + '_gs_orbit'
-        _save_contact_sheet(video, rec['orbit_sheet'], cfg.mean, cfg.std)
-        _save_frames_safe(stem + '_gs_orbit.mp4', video, cfg)
-        if cfg.get('gs_orbit_depth'):
-            rec['orbit_depth'], rec['orbit_depth_sheet'] = stem + '_gs_orbit_depth.npy', stem + '_gs_orbit_depth.png'
-            _save_depth_maps(out["median_depth"][0, :, 0].float().cpu(), rec['orbit_depth'], rec['orbit_depth_sheet'], opt.znear, opt.zfar)
-            logging.info(f"Save {n_orbit} median-depth maps to {rec['orbit_depth']}")
-        if cfg.get('gs_points'):
-            voxel = cfg.get('gs_points_voxel')
-            # default: 1/256 of the camera extent = the width the first orbit camera sees at its distance from the origin of the Gaussians' frame
-            extent = 2.0 * renderer.tan_half_fov * float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
-            voxel = extent / 256.0 if voxel is None else float(voxel)
-            rec['points_ply'] = stem + '_gs_points.ply'
-            rec['points'] = _export_points(out, cv[0], renderer.tan_half_fov, refiner.bg_color, voxel, rec['points_ply'])
-            logging.info(f"Save point cloud ({rec['points']} points, voxel {voxel:.5f}) to {rec['points_ply']}")
-        if cfg.get('gs_mesh'):
-            from .gs_mesh import TsdfVolume, drop_small_components, mesh_stats, save_mesh_ply
-            res, half, trunc = int(cfg.get('gs_mesh_res') or 128), cfg.get('gs_mesh_extent'), cfg.get('gs_mesh_trunc')
-            # default cube: the ball every orbit view sees whole, d sin(fovy / 2) around the origin of the Gaussians' frame
-            cam_dist = float(torch.inverse(cv[0, 0].float().cpu())[3, :3].norm())
-            half = cam_dist * math.sin(0.5 * math.radians(opt.fovy)) if half is None else float(half)
-            vol = TsdfVolume(res, half, trunc=None if trunc is None else float(trunc), device=device)
-            texture = bool(cfg.get('gs_mesh_texture'))
-            fused = []                                                  # with gs_mesh_texture: (depth, colour, cameras) of every fused orbit, in fusion order
-
-            def fuse(o, cams):
-                depth, colour = o["median_depth"][0, :, 0], _unpremultiplied(o, refiner.bg_color)
-                vol.integrate(depth, cams, renderer.tan_half_fov, colour=colour)
-                if texture:
-                    fused.append((depth, colour, cams.to(depth.device)))
-            fuse(out, cv[0])
-            # one more orbit per extra elevation, at the same distance (the default cube is the ball seen whole from that distance, at
-            # any elevation): rendered for the fusion alone
-            for extra in cfg.get('gs_mesh_elevations') or []:
-                cv_e, cvp_e = orbit_cameras(camera_data, n_orbit, float(extra), camera_dist, opt)
-                fuse(renderer.render_depth(g.to(device), cv_e.to(device), cvp_e.to(device), None, bg_color=bgc), cv_e[0])
-            rec['mesh_fused_views'] = vol.n_views
-            verts, cols, faces = vol.extract()
-            dropped = ""
-            if cfg.get('gs_mesh_min_component') is not None:
-                verts, cols, faces, info = drop_small_components(verts, cols, faces, min_fraction=float(cfg.get('gs_mesh_min_component')))
-                rec['mesh_components'], rec['mesh_components_dropped'] = info['components'], info['components'] - info['kept']
-                dropped = (f"; {info['components']} components, {rec['mesh_components_dropped']} dropped with {info['dropped_faces']} faces "
-                           f"and {info['dropped_vertices']} vertices")
-            rec['mesh_ply'] = stem + '_gs_mesh.ply'
-            rec['mesh_vertices'], rec['mesh_faces'] = save_mesh_ply(verts, cols, faces, rec['mesh_ply'])
-            rec['mesh_open_edges'] = mesh_stats(verts, faces)['open_edges']
-            logging.info(f"Save mesh ({rec['mesh_vertices']} vertices, {rec['mesh_faces']} faces, {rec['mesh_open_edges']} open edges; "
-                         f"{res}^3 voxels of {vol.voxel:.5f}, {rec['mesh_fused_views']} views fused{dropped}) to {rec['mesh_ply']}")
-            if texture and rec['mesh_faces'] == 0:
-                logging.info("gs_mesh_texture: the mesh has no faces, no textured mesh is written")
-            elif texture:
-                # the same mesh as a textured .obj: every fused view's colours blended over the surface (gs_mesh_bake.hip), a texel counted
-                # as seen where it lies within 2 voxels of the view's depth map
-                from .gs_mesh import bake_texture, save_mesh_obj
-                patch = int(cfg.get('gs_mesh_texture_patch') or 8)
-                tex, uv, info = bake_texture(verts, cols, faces, *(torch.cat([f[i] for f in fused]) for i in range(3)), renderer.tan_half_fov,
-                                             patch=patch, depth_tol=2.0 * vol.voxel)
-                rec['mesh_obj'] = stem + '_gs_mesh.obj'
-                save_mesh_obj(verts, faces, uv, tex, stem + '_gs_mesh')
-                rec['mesh_texture_size'], rec['mesh_texels_baked'] = info['size'], info['baked']
-                logging.info(f"Save textured mesh ({info['size']} x {info['size']} texture, patch {patch}, {info['texels']} texels of faces, "
-                             f"{100 * info['baked']:.1f} % baked from {len(fused) * n_orbit} views, {100 * info['fallback']:.1f} % vertex colours) "
-                             f"to {rec['mesh_obj']}")
-    return rec
-
-
-def _save_depth_maps(depth, npy_path, png_path, znear, zfar):
-    """depth [n, S, S] (median depth, 0 = no surface) -> the float32 array as .npy and an 8-bit contact sheet: znear .. zfar mapped
-    linearly to white .. black, no-surface pixels black."""
-    import numpy as np
-    d = depth.numpy().astype(np.float32)
-    np.save(npy_path, d)
-    try:
-        from PIL import Image
-        shade = np.clip((zfar - d) / (zfar - znear), 0.0, 1.0)
-        shade[d <= 0] = 0.0
-        Image.fromarray(np.concatenate(list(np.round(shade * 255.0).astype(np.uint8)), axis=1)).save(png_path)
-    except Exception as e:  # pragma: no cover
-        logging.info(f'Step: save png error with {e}')
-
-
-def _unpremultiplied(out, bg):
-    """The colour of the surface in every view of ``out`` (GaussianRenderer.render_depth, sample 0), the background taken out:
-    clamp((image - (1 - alpha) bg) / alpha, 0, 1) -> [V, 3, S, S]"""
-    a = out["alpha"][0]
-    return ((out["image"][0] - (1.0 - a) * bg) / a.clamp_min(1e-6)).clamp(0, 1)
-
-
-def _export_points(out, cam_view, tan_half_fov, bg, voxel, path):
-    """The pixels of every view of ``out`` (GaussianRenderer.render_depth, sample 0) that have a median depth, unprojected to world
-    points and coloured with the un-premultiplied render (``_unpremultiplied``), merged per voxel, written as a .ply.  Deterministic,
-    no RNG.  -> the number of points."""
-    from .gs import depth_to_points, merge_points_voxel, save_points_ply
-    colour = _unpremultiplied(out, bg)
-    pts, cols = [], []
-    for v in range(cam_view.shape[0]):
-        p, idx = depth_to_points(out["median_depth"][0, v, 0], cam_view[v], tan_half_fov)
-        pts.append(p)
-        cols.append(colour[v].reshape(3, -1)[:, idx].t())
-    pts, cols = torch.cat(pts).float().cpu(), torch.cat(cols).float().cpu()
-    if pts.shape[0] > 0:
-        pts, cols = merge_points_voxel(pts, cols, voxel)
-    return save_points_ply(pts, cols, path)
-
-
-def _save_frames_safe(local_path, video, cfg):
-    try:                                            # (inference_text2video_entrance.py:296-300: errors are logged, not raised)
-        save_video_frames(local_path, video, cfg.mean, cfg.std)
-        logging.info('Save video to dir %s:' % local_path)
-    except Exception as e:
-        logging.info(f'Step: save text or video error with {e}')
-
-
-def save_video_frames(local_path, gen_video, mean, std, save_fps=8):
-    """The reference writer's outputs (utils/video_op.py:166-211, ``save_i2vgen_video_safe``) as far as this image allows:
-    the de-normalised frames ``clamp(v * std + mean, 0, 1) * 255`` truncated to uint8, one PNG per view named
-    ``<local_path minus .mp4>/{fid:05d}.png`` (written by cv2 in the reference, PIL here: same pixels), and
-    ``<local_path>`` itself — an H.264 mp4 at ``save_fps`` — when an encoder exists (``imageio`` with ffmpeg, or an ``ffmpeg``
-    binary on PATH; neither ships in this image, in which case only the PNGs are written and the fact is logged).
-    A single-frame video becomes ``<local_path>.png`` as in the reference.  Returns the list of files written."""
-    import shutil
-    import subprocess
-    import numpy as np
-    from PIL import Image
-    v = gen_video.detach().float().cpu()
-    v = v * torch.tensor(std).view(1, -1, 1, 1, 1) + torch.tensor(mean).view(1, -1, 1, 1, 1)
-    v = (v.clamp(0, 1) * 255.0)[0].permute(1, 2, 3, 0)                   # f h w c  (the reference saves sample 0)
-    frames = [f.numpy().astype('uint8') for f in v]                      # astype truncates, as the reference does
-    written = []
-    if len(frames) == 1:
-        Image.fromarray(frames[0]).save(local_path + '.png')
-        return [local_path + '.png']
-    frame_dir = local_path.replace('.mp4', '')
-    os.makedirs(frame_dir, exist_ok=True)
-    for fid, frame in enumerate(frames):
-        fp = os.path.join(frame_dir, '{:05d}.png'.format(fid))
-        Image.fromarray(frame).save(fp)
-        written.append(fp)
-    try:
-        import imageio                                                    # the reference's encoder
-        writer = imageio.get_writer(local_path, fps=save_fps, codec='libx264', quality=8)
-        for frame in frames:
-            writer.append_data(frame)
-        writer.close()
-        written.append(local_path)
-    except Exception:
-        exe = shutil.which('ffmpeg')
-        if exe is not None:
-            cmd = [exe, '-y', '-loglevel', 'quiet', '-framerate', str(save_fps), '-start_number', '0', '-i',
-                   os.path.join(frame_dir, '%05d.png'), '-vcodec', 'libx264', '-crf', '17', '-pix_fmt', 'yuv420p', local_path]
-            if subprocess.run(cmd).returncode == 0:
-                written.append(local_path)
-        else:
-            logging.info(f'no H.264 encoder in this environment (imageio / ffmpeg): wrote {len(frames)} PNG frames to {frame_dir}')
-    return written
-
-
-def _save_contact_sheet(video, path, mean, std):
-    """video [1, 3, F, H, W] in normalised range -> one PNG with the F views side by side (best effort)."""
-    try:
-        from PIL import Image
-        v = video[0].permute(1, 2, 3, 0).float()                     # F H W C
-        v = (v * torch.tensor(std) + torch.tensor(mean)).clamp(0, 1)
-        sheet = torch.cat(list(v), dim=1)                            # H, F*W, C
-        Image.fromarray((sheet * 255).round().byte().numpy()).save(path)
-    except Exception as e:  # pragma: no cover
-        logging.info(f'Step: save png error with {e}')
+    return _finish(cfg, model, on_gpu, outputs, gs_exports)

@@ -22,6 +22,26 @@ from . import _lib as L
 PLANES = ("tsdf", "weight", "behind", "red", "green", "blue", "colour_weight")
 
 
+def _view_tensors(depth, colour, cam_view, dev):
+    """The views as the kernels read them: contiguous fp32 depth [V, S, S], colour [V, 3, S, S] (or None) and cameras [V, 16] on ``dev``."""
+    V, S = int(depth.shape[0]), int(depth.shape[-1])
+    d, col, views = depth.reshape(V, S, S), None if colour is None else colour.reshape(V, 3, S, S), cam_view.reshape(V, 16)
+    return tuple(t if t is None else t.to(dev, torch.float32).contiguous() for t in (d, col, views))
+
+
+def _kernel_faces(faces):
+    """``faces`` as the kernels read them: the three indices of a face adjacent, a face stride >= 3"""
+    return faces if faces.stride(1) == 1 and faces.stride(0) >= 3 else faces.contiguous()
+
+
+def _raise_status(status, what, n):
+    """The status word of vmv_gs_mesh_components / vmv_gs_mesh_bake (bits: _lib.MESH_STATUS_*), or of a CPU path, as its exception."""
+    if status & L.MESH_STATUS_GAVE_UP:
+        raise RuntimeError(f"{what}: a bounded loop of the union-find gave up (status bit 1): the label buffer was written during the call")
+    if status & L.MESH_STATUS_RANGE:
+        raise ValueError(f"{what}: a face names a vertex outside [0, {n})")
+
+
 class TsdfVolume:
     """res^3 voxel CENTRES over the cube centre +- half_extent: voxel = 2 half_extent / res, centre i at origin + i * voxel with
     origin = centre - half_extent + voxel / 2.  ``acc`` [7, res, res, res] (planes of VmvGsTsdfParams, [z][y][x]) starts at zero."""
@@ -42,10 +62,8 @@ class TsdfVolume:
         dev = self.acc.device
         if dev.type != "cuda":
             raise RuntimeError("TsdfVolume.integrate runs the HIP kernel: the volume must live on a GPU (there is no CPU fallback)")
-        V, S = int(depth.shape[0]), int(depth.shape[-1])
-        d = depth.to(dev, torch.float32).reshape(V, S, S).contiguous()
-        views = cam_view.to(dev, torch.float32).reshape(V, 16).contiguous()
-        col = None if colour is None else colour.to(dev, torch.float32).reshape(V, 3, S, S).contiguous()
+        d, col, views = _view_tensors(depth, colour, cam_view, dev)
+        V, S = d.shape[:2]
         p = L.GsTsdfParams()
         p.depth, p.colour, p.views = d.data_ptr(), None if col is None else col.data_ptr(), views.data_ptr()
         p.n_views, p.size, p.tan_half_fov, p.res = V, S, float(tan_half_fov), self.res
@@ -192,29 +210,18 @@ def mesh_components(faces, n_vertices):
     current stream; CPU tensors the torch propagation above.  A face index outside [0, n_vertices) raises ValueError."""
     n, m = int(n_vertices), int(faces.shape[0])
     assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64 and n >= 0
-    out_of_range = f"mesh_components: a face names a vertex outside [0, {n})"
-    if n == 0:
-        if m:
-            raise ValueError(out_of_range)
-        return (torch.zeros(0, dtype=torch.int64, device=faces.device),) * 2
-    if not faces.is_cuda:
-        if m and bool(((faces < 0) | (faces >= n)).any()):
-            raise ValueError(out_of_range)
-        return _components_eager(faces, n)
+    if n == 0 or not faces.is_cuda:                                     # (the kernel takes n >= 1: no vertices, no launch)
+        _raise_status(L.MESH_STATUS_RANGE if m and bool(((faces < 0) | (faces >= n)).any()) else 0, "mesh_components", n)
+        return _components_eager(faces, n) if n else (torch.zeros(0, dtype=torch.int64, device=faces.device),) * 2
     from .ops import _stream_ptr
-    if m and not (faces.stride(1) == 1 and faces.stride(0) >= 3):
-        faces = faces.contiguous()
+    faces = _kernel_faces(faces)
     out = torch.empty(2 * n + 1, dtype=torch.int32, device=faces.device)
     p = L.GsMeshComponentsParams()
     p.faces = faces.data_ptr() if m else out.data_ptr()                 # no face is read when there is none
     p.face_stride, p.n_faces, p.n_vertices = (int(faces.stride(0)) if m else 3), m, n
     p.label, p.face_count, p.status = out.data_ptr(), out.data_ptr() + 4 * n, out.data_ptr() + 8 * n
     L.check(L.load().vmv_gs_mesh_components(C.byref(p), _stream_ptr()), "gs_mesh_components")
-    status = int(out[2 * n])
-    if status & 2:
-        raise RuntimeError("mesh_components: a bounded loop of the union-find gave up (status bit 1): the label buffer was written during the call")
-    if status & 1:
-        raise ValueError(out_of_range)
+    _raise_status(int(out[2 * n]), "mesh_components", n)
     return out[:n].long(), out[n:2 * n].long()
 
 
@@ -394,24 +401,19 @@ def bake_texture(verts, colours, faces, depth, colour, cam_view, tan_half_fov, p
     if not 0.0 <= float(cos_min) < 1.0:
         raise ValueError(f"bake_texture: cos_min must be in [0, 1), got {cos_min}")
     dev = verts.device
-    V, S = int(depth.shape[0]), int(depth.shape[-1])
     verts, colours = verts.to(torch.float32).contiguous(), colours.to(dev, torch.float32).contiguous()
     if depth_tol is None:
         depth_tol = 0.01 * float((verts.max(0).values - verts.min(0).values).norm())
     if not float(depth_tol) > 0:
         raise ValueError(f"bake_texture: depth_tol must be positive, got {depth_tol}")
-    d = depth.to(dev, torch.float32).reshape(V, S, S).contiguous()
-    col = colour.to(dev, torch.float32).reshape(V, 3, S, S).contiguous()
-    views = cam_view.to(dev, torch.float32).reshape(V, 4, 4).contiguous()
-    out_of_range = f"bake_texture: a face names a vertex outside [0, {n})"
+    d, col, views = _view_tensors(depth, colour, cam_view, dev)
+    V, S = d.shape[:2]
     if dev.type != "cuda":
-        tex, bad = _bake_eager(verts, colours, faces, d, col, views, float(tan_half_fov), P, T, float(depth_tol), float(cos_min), float(z_min))
-        if bool(bad):
-            raise ValueError(out_of_range)
+        tex, bad = _bake_eager(verts, colours, faces, d, col, views.reshape(V, 4, 4), float(tan_half_fov), P, T, float(depth_tol), float(cos_min), float(z_min))
+        _raise_status(L.MESH_STATUS_RANGE if bool(bad) else 0, "bake_texture", n)
     else:
         from .ops import _stream_ptr
-        if not (faces.stride(1) == 1 and faces.stride(0) >= 3):
-            faces = faces.contiguous()
+        faces = _kernel_faces(faces)
         tex = torch.empty(4, T, T, dtype=torch.float32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
         p = L.GsMeshBakeParams()
@@ -421,8 +423,7 @@ def bake_texture(verts, colours, faces, depth, colour, cam_view, tan_half_fov, p
         p.z_min, p.depth_tol, p.cos_min, p.patch, p.tex_size = float(z_min), float(depth_tol), float(cos_min), P, T
         p.out, p.plane_stride, p.status = tex.data_ptr(), T * T, status.data_ptr()
         L.check(L.load().vmv_gs_mesh_bake(C.byref(p), _stream_ptr()), "gs_mesh_bake")
-        if int(status) & 1:
-            raise ValueError(out_of_range)
+        _raise_status(int(status), "bake_texture", n)
     owned = int((tex[3] >= 0).sum())
     baked = int((tex[3] > 0).sum())
     info = dict(size=T, texels=owned, baked=baked / max(owned, 1), fallback=(owned - baked) / max(owned, 1))
