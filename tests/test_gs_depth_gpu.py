@@ -12,6 +12,7 @@ import torch
 
 from oracle.gs_ref import render as oracle_render
 from tests import footprint as FP
+from tests import gs_stage_ref as R
 from tests.gs_depth_ref import blend_depth, blend_depth_views, compare_view, staging_scene
 from tests.test_gs_gpu import _cams, _scene
 
@@ -40,7 +41,8 @@ def _rendered(n, size, big, seed):
     out = r.render_depth(*args, bg_color=torch.tensor(BG).cuda())
     plain = r.render(*args, bg_color=torch.tensor(BG).cuda())
     torch.cuda.synchronize()
-    return {k: v.cpu() for k, v in out.items()}, {k: v.cpu() for k, v in plain.items()}
+    arrays = R.read_arrays(r.binning(1, 3, n, args[0].device))          # what the pass left on the device (the two passes: the same bits)
+    return {k: v.cpu() for k, v in out.items()}, {k: v.cpu() for k, v in plain.items()}, arrays
 
 
 @pytest.mark.parametrize("n,size,big,seed", SCENES)
@@ -48,7 +50,7 @@ def test_expected_depth_matches_the_oracle(n, size, big, seed):
     """depth / z_max is a colour channel with values in (0, 1] — the same weighted sum — so it is held to the rasteriser's colour bound
     against the oracle's third return value; image and alpha are render()'s bits."""
     g, cv, cvp, refs = _reference(n, size, big, seed)
-    out, plain = _rendered(n, size, big, seed)
+    out, plain, _ = _rendered(n, size, big, seed)
     assert out["depth"].shape == out["median_depth"].shape == (1, 3, 1, size, size) and out["depth"].dtype == torch.float32
     assert torch.equal(out["image"], plain["image"]) and torch.equal(out["alpha"], plain["alpha"])
     for v in range(3):
@@ -61,14 +63,19 @@ def test_expected_depth_matches_the_oracle(n, size, big, seed):
 
 @pytest.mark.parametrize("n,size,big,seed", SCENES)
 def test_median_depth_matches_the_reference(n, size, big, seed):
-    _, _, _, refs = _reference(n, size, big, seed)
-    out, _ = _rendered(n, size, big, seed)
+    g, _, _, refs = _reference(n, size, big, seed)
+    out, _, arrays = _rendered(n, size, big, seed)
     for v in range(3):
         fig = compare_view(out["depth"][0, v, 0], out["median_depth"][0, v, 0], refs[v], f"scene {seed} view {v}")
         if n == 300:              # the sparse scene shows both branches: pixels with a median and pixels without
             assert 0.17 <= fig["with_median"] <= 0.20, fig
             assert bool(refs[v]["has"].any()) and bool((~refs[v]["has"]).any())
             assert bool((out["median_depth"][0, v, 0] > 0).any()) and bool((out["median_depth"][0, v, 0] == 0).any())
+    if n == 300:
+        # beside compare_view's statistical bounds: this pass's binning exact, and at every non-ambiguous pixel the median the reference's
+        # own Gaussian and image, alpha and expected depth within the per-pixel bound of tests/gs_stage_ref.py
+        R.check_views_per_pixel(arrays, g.unsqueeze(0), 3, size, BG, f"depth scene {seed}", image=out["image"][0], alpha=out["alpha"][0, :, 0],
+                                depth=out["depth"][0, :, 0], median=out["median_depth"][0, :, 0])
 
 
 def _identity_render(g, size, bg=(0.0, 0.0, 0.0)):

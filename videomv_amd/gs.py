@@ -121,7 +121,7 @@ class GaussianRenderer:
             i32 = lambda: torch.zeros(cap, dtype=torch.int32, device=device)
             buf.update(keys=i64(), keys_s=i64(), vals=i32(), vals_s=i32(), cap=cap,
                        sort=torch.zeros(max(int(so.value), 16), dtype=torch.uint8, device=device))
-        p.num_rendered = n
+        p.num_rendered = buf["n"] = n
         if n > 0:
             p.keys, p.keys_sorted, p.vals, p.vals_sorted = (buf["keys"].data_ptr(), buf["keys_s"].data_ptr(), buf["vals"].data_ptr(),
                                                             buf["vals_s"].data_ptr())
@@ -152,6 +152,32 @@ class GaussianRenderer:
                      total=torch.zeros(1, dtype=torch.int32).pin_memory() if str(device).startswith("cuda") else torch.zeros(1, dtype=torch.int32))
             self._buf[key] = b
         return b
+
+    @staticmethod
+    def _stage_arrays(buf, shape, n, key_dtype):
+        """views (no copy, no device work) of what the last pass over ``buf`` left on the device; ``shape`` = the leading dimensions of the
+        per-Gaussian arrays, ``key_dtype`` = the form of key that pass sorted (they are the first n entries of the key buffer)"""
+        empty = lambda dt: torch.empty(0, dtype=dt, device=buf["depth"].device)
+        has = n > 0 and "keys_s" in buf
+        return dict(n=n, depth=buf["depth"].view(*shape), xy=buf["xy"].view(*shape, 2), conic_opacity=buf["co"].view(*shape, 4),
+                    rect=buf["rect"].view(*shape, 4), tiles_touched=buf["touched"].view(*shape), offsets=buf["offsets"].view(*shape),
+                    ranges=buf["ranges"].view(*shape[:-1], -1, 2),
+                    keys_sorted=buf["keys_s"].view(key_dtype)[:n] if has else empty(key_dtype),
+                    vals_sorted=buf["vals_s"][:n] if has else empty(torch.int32))
+
+    def binning(self, B, V, N, device):
+        """The intermediate arrays of the last BATCHED pass at this shape (``render``, ``render_depth``, GaussianFitter's forward), read
+        only: n (the instance total), depth / tiles_touched / offsets [B * V, N], xy [B * V, N, 2], conic_opacity [B * V, N, 4],
+        rect [B * V, N, 4] (records with tiles_touched == 0 keep whatever they held), ranges [B * V, tiles, 2], and the first n sorted
+        (view, tile) keys (int32) and values (the Gaussian's index in its sample).  ``offsets`` are in depth-rank order."""
+        buf = self._buf[("batch", B, V, N, str(device))]
+        return self._stage_arrays(buf, (B * V, N), buf.get("n", 0), torch.int32)
+
+    def binning_view(self, N, device):
+        """``binning`` for the per-view path (VMV_GS_BATCH=0): the arrays of the LAST view rendered, leading dimension 1, the keys in
+        that path's form (int64: tile << 32 | depth bits), ``offsets`` in index order."""
+        buf = self._buf[(N, str(device))]
+        return self._stage_arrays(buf, (1, N), buf.get("n", 0), torch.int64)
 
     def _batch_setup(self, p, gaussians, views, view_projs, B, V, N, bg, limit):
         """Everything of one batched pass before its blend, for the renderer and for GaussianFitter: fills ``p`` (GsBatchParams) from
